@@ -9,7 +9,13 @@ is fixed as N grows: "strong".  Under torchrun
 WORLD_SIZE must equal N; without a launcher and N > 1 the bench starts N ranks itself
 (torch.distributed.run, child process); it exits non-zero rather than render N > 1 on one GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--no-cpu]
+A plain run sets up, warms up, times the K steps and prints one JSON line (the roofline fields
+come from the per-kernel events of the timed steps themselves and cost no run of their own).
+--full adds what takes a run of its own: the CPU baseline (the oracle on every CPU; --no-cpu
+drops it again).  --dump-outputs DIR writes the frame of the last timed step (rank 0's
+assembled framebuffer, what a caller of the timed path receives) as DIR/frame.npy, float32.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--full [--no-cpu]] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -96,6 +102,24 @@ def cpu_baseline(cfg_name, cfg, spp=None):
                       + (f", cgroup CPU quota {quota:g}" if quota else "") + f"), {dt:.2f} s wall"}
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, the
+    (H, W, 3) float32 frame, as path/frame.npy.  A frame above DUMP_MAX_BYTES is cut to a fixed,
+    seeded sample of its pixels (their row-major indices go to path/frame_pixels.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    budget = DUMP_MAX_BYTES // (3 * 4 + 8)
+    if frame.shape[0] * frame.shape[1] > budget:
+        idx = np.sort(np.random.default_rng(0).choice(frame.shape[0] * frame.shape[1], budget, replace=False))
+        np.save(os.path.join(path, "frame_pixels.npy"), idx.astype(np.float64))
+        frame = frame.reshape(-1, 3)[idx]
+    np.save(os.path.join(path, "frame.npy"), frame)
+
+
 def plan_launch(gpus, env, device_count):
     """How `bench.py --gpus N` runs (decided before any GPU call):
     ("run", world)  — this process is one rank of `world` (torchrun set WORLD_SIZE = N, or N = 1);
@@ -169,7 +193,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--spp", type=int, default=None, help="override spp (never for reported numbers)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes a run of its own: the CPU baseline (1 GPU; see --no-cpu)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's frame (rank 0) as DIR/frame.npy, float32")
     ap.add_argument("--cpu-spp", type=int, default=None, help="override the CPU sample's spp")
     ap.add_argument("--no-timing", action="store_true", help="skip per-kernel HIP events")
     ap.add_argument("--schedule", default="auto", choices=("auto", "step", "wavefront"))
@@ -181,6 +209,8 @@ def main():
     ap.add_argument("--test-standin", default=None, metavar="MODULE:FACTORY",
                     help="TESTS ONLY (tests/test_bench_launch.py): a CPU stand-in renderer instead of the HIP one")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error(f"--steps must be >= 1, got {args.steps}")
     args.traffic = args.traffic or os.path.join(ROOT, "profiles", f"traffic_{args.config}.json")
     args.pmc = args.pmc or os.path.join(ROOT, "profiles", f"pmc_{args.config}.json")
 
@@ -284,6 +314,9 @@ def main():
         elapsed = distributed.max_over_ranks(elapsed, dist, device=dev)
         reduce_s = distributed.max_over_ranks(reduce_s, dist, device=dev)
         agg = distributed.sum_counters(agg, dist, device=dev)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, fb.cpu().numpy())
 
     if rank == 0:
         total_samples = W * H * SPP * args.steps
@@ -409,7 +442,7 @@ def main():
             out["config"]["assembly"] = args.assembly
             out["config"]["assembly_ms_per_step"] = round(reduce_s / args.steps * 1e3, 3)
             out["config"]["assembly_bytes"] = distributed.assembly_bytes(H, W, world, args.assembly)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.config, cfg, args.cpu_spp)
         print(json.dumps(out), flush=True)
     r.close()

@@ -90,6 +90,57 @@ def test_bench_spawns_two_ranks_end_to_end(tmp_path):
     assert open(tmp_path / "frames.1").read().split()[0] == "4"
 
 
+def _one_rank(tmp_path, *args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "2",
+                        "--warmup", "1", "--no-timing", "--test-standin", "bench_standin:make", *args],
+                       capture_output=True, text=True, env=_standin_env(tmp_path), timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return lines[0]
+
+
+def test_bench_plain_run_dumps_last_frame(tmp_path):
+    """A plain run (no --full) times its steps and nothing else — no CPU baseline — and
+    --dump-outputs DIR leaves the last timed step's frame as DIR/frame.npy in float32: with the
+    stand-in renderer, row y of the (256, 256, 3) C1 frame holds y + 1."""
+    import numpy as np
+    d = _one_rank(tmp_path, "--dump-outputs", str(tmp_path / "dump"))
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None
+    assert open(tmp_path / "frames.0").read().split()[0] == "3"   # warmup + exactly --steps renders
+    assert os.listdir(tmp_path / "dump") == ["frame.npy"]
+    frame = np.load(tmp_path / "dump" / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (256, 256, 3)
+    assert np.array_equal(frame, np.broadcast_to((np.arange(256, dtype=np.float32) + 1)[:, None, None], frame.shape))
+
+
+def test_bench_full_adds_cpu_baseline(tmp_path):
+    """--full brings back what a plain run leaves out: the oracle's CPU baseline (here at 1 spp)."""
+    d = _one_rank(tmp_path, "--full", "--cpu-spp", "1")
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["unit"] == "Msamples/s"
+    d = _one_rank(tmp_path, "--full", "--no-cpu")
+    assert d["cpu_baseline"] is None
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """A frame above the dump's size limit is cut to a fixed, seeded sample of its pixels."""
+    import numpy as np
+    frame = np.arange(40 * 50 * 3, dtype=np.float32).reshape(40, 50, 3)
+    limit, bench.DUMP_MAX_BYTES = bench.DUMP_MAX_BYTES, 100 * 20
+    try:
+        bench.dump_outputs(str(tmp_path / "a"), frame)
+        bench.dump_outputs(str(tmp_path / "b"), frame)
+    finally:
+        bench.DUMP_MAX_BYTES = limit
+    got, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixels.npy")
+    assert got.dtype == np.float32 and got.shape == (100, 3) and idx.dtype == np.float64
+    assert got.nbytes + idx.nbytes <= 100 * 20 and len(np.unique(idx)) == 100
+    assert np.array_equal(got, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "frame.npy"))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_pixels.npy"))
+
+
 def test_bench_failing_rank_fails_the_job(tmp_path):
     """A rank that raises ends the job with a non-zero status and no bench line."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu", "--config", "C1",

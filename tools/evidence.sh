@@ -2,8 +2,8 @@
 # tools/evidence.sh TAG [CONFIG] — the measurement evidence of a round, on the GPU box:
 #   1. rocprofv3 kernel-trace/stats + PMC passes of bench.py (tools/profile.sh)
 #   2. per-launch HBM traffic / SQ counters of the dominant kernel -> profiles/{traffic,pmc}_CONFIG.json
-#   3. the default bench.py line (with the CPU baseline) -> gpurun_out/TAG/bench.json
-# Copy gpurun_out/TAG/{kt_kernel_stats.csv,summary.txt,bench.json} into profiles/ after.
+#   3. the bench.py --full line (with the CPU baseline) -> stdout, the last line
+# Copy kt_kernel_stats.csv and summary.txt from the TAG output folder, and that line, into profiles/ after.
 set -euo pipefail
 TAG=$1; CFG=${2:-C2}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -26,5 +26,5 @@ cp "$R/gpurun_out/$TAG/kt/kt_kernel_stats.csv" "$R/gpurun_out/$TAG/kt_kernel_sta
 gzip -f "$R/gpurun_out/$TAG/pmc_dispatch.csv"
 rm -rf "$R/gpurun_out/$TAG"/{kt,sq1,sq2,fetch,write}
 mkdir -p "$R/gpurun_out/profiles_new" && cp "$R/profiles/traffic_$CFG.json" "$R/profiles/pmc_$CFG.json" "$R/gpurun_out/profiles_new/"
-timeout -k 10 600 python3 "$R/bench.py" --config "$CFG" > "$R/gpurun_out/$TAG/bench.json"
-cat "$R/gpurun_out/$TAG/bench.json"
+# the full bench line (--full: with the CPU baseline) is this script's last line of output
+timeout -k 10 600 python3 "$R/bench.py" --config "$CFG" --full

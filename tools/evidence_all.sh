@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/evidence_all.sh TAG [CONFIGS...] — tools/evidence.sh for each config (default C3 C4 C5
-# C2): rocprof kernel trace + PMC passes + per-config profiles/{pmc,traffic}_CONFIG.json + the
-# default bench line with its CPU baseline, into gpurun_out/TAG_CONFIG/.
+# C2): rocprof kernel trace + PMC passes + per-config profiles/{pmc,traffic}_CONFIG.json into
+# the TAG_CONFIG output folder, + the bench.py --full line with its CPU baseline (printed last).
 set -euo pipefail
 TAG=$1; shift
 CFGS=${*:-C3 C4 C5 C2}
