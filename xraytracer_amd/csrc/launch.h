@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "wavefront.h"
 
@@ -16,6 +17,30 @@ inline const char* exp_env(const char* name) { return std::getenv(name); }
 #else
 inline const char* exp_env(const char*) { return nullptr; }
 #endif
+// Runtime value -> template argument, for launchers whose kernels are instantiated per scene
+// kind, integrator or light count: calls fn(std::integral_constant<int, V>{}) for the first listed V that
+// equals v (the last one when none does) and returns what fn returns.  fn is a generic lambda
+// that uses its argument as a constant expression (`k_shade<SCN, I>`); a build that exists for
+// some values only is an `if constexpr (I == ...)` inside it, so exactly the kernels the
+// lambda names for the listed values are instantiated.
+template <int V, int... Rest, typename F>
+auto with_const(int v, F&& fn) {
+    if constexpr (sizeof...(Rest) == 0) {
+        return fn(std::integral_constant<int, V>{});
+    } else {
+        if (v == V) return fn(std::integral_constant<int, V>{});
+        return with_const<Rest...>(v, fn);
+    }
+}
+template <typename F>
+auto with_scene_kind(int kind, F&& fn) {
+    return with_const<SCN_TRI, SCN_SPHERE, SCN_MIXED>(kind, fn);
+}
+template <typename F>
+auto with_integrator(int integrator, F&& fn) {
+    return with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_VPT, XRT_INTEGRATOR_INDIRECT, XRT_INTEGRATOR_NORMAL,
+                      XRT_INTEGRATOR_VPT_NEE, XRT_INTEGRATOR_GI>(integrator, fn);
+}
 hipError_t launch_seed(const KParams& P, uint32_t* list, uint32_t* count, uint32_t* count_other,
                        uint32_t* req_count, hipStream_t st);
 // twist the rings of the slots on P.req (count at *count); clears *zero_count
@@ -44,9 +69,10 @@ hipError_t launch_pixel(const KParams& P, uint32_t* work, hipStream_t st);
 // (next-next round).  req_count is unused by the step kernels (kept in the signature of
 // every schedule's step launch; only the seeding k_refill reads the request list)
 // dP: device copy of P (the triangle-scene kernel reads its parameters from memory)
+// tri: the caller's use_step_tri(P), decided once per render (k_step_tri instead of k_step)
 hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count, uint32_t* out,
                        uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
-                       uint64_t live, hipStream_t st);
+                       uint64_t live, bool tri, hipStream_t st);
 // merged-trace triangle schedule (step_tri.hip): eligibility, RNG words one segment may
 // draw, LDS bytes, the per-object kernel-argument records, and the launch (same list /
 // counter contract as launch_step)

@@ -624,23 +624,16 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
             const bool act = live && !(st & ST_DONE) && g - rng.c >= (uint32_t)NW;
             if (!__ballot(act || shm)) break;
             const bool ext_now = act && ext;
-            // a sample's camera ray (depth 0) is tested against its pixel's camera list
-            // (k_camlist, spec.hip: the triangles a camera ray of the pixel can hit, or the one
-            // every such ray hits first) instead of taking part in the trace
-            const bool cam = XRT_MERGED_CAMLIST && !BVH && P.camlist && ext_now && depth == 0;
-            uint4 cl = make_uint4(0u, 0u, 0xffffffffu, 0u);
-            if (cam) cl = P.camlist[s];   // used after the trace: its latency hides behind it
             unsigned long long best;
             uint32_t occ;
             if constexpr (BVH) {
                 merged_trace<NL, true>(SO, L, W, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
                 deep_pass<NL, uint16_t>(P, top, ntop, stk, W, lane, root, ext_now, o, d, shm, so, sd, stm, best, occ);
             } else if constexpr (!LANE) {
-                merged_trace<NL>(SO, L, W, lane, ext_now && !cam, o, d, shm, so, sd, stm, best, occ);
+                merged_trace<NL>(SO, L, W, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
             } else {
-                group_trace<NL, G>(P.n_objs, L, lplane, lane, ext_now && !cam, o, d, shm, so, sd, stm, best, occ);
+                group_trace<NL, G>(P.n_objs, L, lplane, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
             }
-            if (cam) best = camlist_closest(L, cl, o, d);
             resolve(occ);
             if (BVH ? pf_pending : vis > 0) rng.take();   // the words prefetched at the end of the previous segment
             if (ext_now) {
@@ -867,13 +860,7 @@ bool use_step_bvh(const KParams& P) {
 uint32_t step_merged_draws(const KParams& P) { return 6u + 2u * (uint32_t)P.n_lights; }
 
 static size_t merged_wave_bytes(int n_lights) {
-    switch (n_lights) {
-        case 0: return sizeof(MergedWave<0>);
-        case 1: return sizeof(MergedWave<1>);
-        case 2: return sizeof(MergedWave<2>);
-        case 3: return sizeof(MergedWave<3>);
-        default: return sizeof(MergedWave<4>);
-    }
+    return with_const<0, 1, 2, 3, 4>(n_lights, [](auto nl) { return sizeof(MergedWave<decltype(nl)::value>); });
 }
 
 size_t step_merged_lds_bytes(const KParams& P) {
@@ -906,22 +893,12 @@ static void launch_merged_i(const KParams& P, const KParams* dP, const StepObjs&
     // any remainder, so an upper bound on the live count is all the grid needs)
     const uint32_t per_block = (kBlock / 64) * SPW;
     const uint32_t blocks = P.n_part * ((std::min(part_live, P.part_cap) + per_block - 1) / per_block);
-#define XRT_LAUNCH_MERGED(NLV)                                                                                       \
-    hipLaunchKernelGGL((k_step_merged<INTEG, NLV, SPW, G, LANE, BVH, WV>), dim3(blocks), dim3(kBlock), lds, st, dP, SO, list, \
-                       count, out, out_count, zero, req_count, visits)
-    if constexpr (BVH) {   // use_step_bvh: 1 or 2 lights
-        if (P.n_lights == 1) XRT_LAUNCH_MERGED(1);
-        else XRT_LAUNCH_MERGED(2);
-    } else {
-        switch (P.n_lights) {
-            case 0: XRT_LAUNCH_MERGED(0); break;
-            case 1: XRT_LAUNCH_MERGED(1); break;
-            case 2: XRT_LAUNCH_MERGED(2); break;
-            case 3: XRT_LAUNCH_MERGED(3); break;
-            default: XRT_LAUNCH_MERGED(4); break;
-        }
-    }
-#undef XRT_LAUNCH_MERGED
+    auto go = [&](auto nl) {
+        hipLaunchKernelGGL((k_step_merged<INTEG, decltype(nl)::value, SPW, G, LANE, BVH, WV>), dim3(blocks), dim3(kBlock), lds,
+                           st, dP, SO, list, count, out, out_count, zero, req_count, visits);
+    };
+    if constexpr (BVH) with_const<1, 2>(P.n_lights, go);   // use_step_bvh: 1 or 2 lights
+    else with_const<0, 1, 2, 3, 4>(P.n_lights, go);
 }
 
 // slots per wave for a shard of `live` slots
@@ -996,12 +973,10 @@ hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObj
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
                               hipStream_t st) {
     const size_t lds = step_merged_lds_bytes(P);
-    if (P.integrator == XRT_INTEGRATOR_DIRECT)
-        launch_merged_spw<XRT_INTEGRATOR_DIRECT>(P, dP, SO, list, count, out, out_count, zero, req_count, visits,
-                                                 live, live_part_max, lds, st);
-    else
-        launch_merged_spw<XRT_INTEGRATOR_GI>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, live,
-                                             live_part_max, lds, st);
+    with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {   // use_step_merged / _bvh
+        launch_merged_spw<decltype(integ)::value>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, live,
+                                                  live_part_max, lds, st);
+    });
     return hipGetLastError();
 }
 

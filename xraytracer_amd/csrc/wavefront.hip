@@ -2270,16 +2270,6 @@ hipError_t launch_seed(const KParams& P, uint32_t* list, uint32_t* count, uint32
 }
 
 
-template <int SCN>
-static hipError_t trace_nl(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
-                           uint32_t blocks, hipStream_t st) {
-    if (P.n_lights <= 1)
-        hipLaunchKernelGGL((k_trace<SCN, 1>), dim3(blocks), dim3(kBlock), 0, st, P, list, count, zero);
-    else
-        hipLaunchKernelGGL((k_trace<SCN, kMaxLights>), dim3(blocks), dim3(kBlock), 0, st, P, list, count, zero);
-    return hipGetLastError();
-}
-
 // Phase B of the two-level trace (P.two_level): the 4-wide BVH walk of the rays phase A
 // queued.  Persistent: up to 2048 blocks (8 per CU), each serving partition blockIdx % n_part.
 // A no-op for every other trace.
@@ -2305,87 +2295,57 @@ hipError_t launch_trace_deep(const KParams& P, hipStream_t st) {
 
 hipError_t launch_trace(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
                         uint32_t blocks, hipStream_t st, bool zero_deep) {
-    if (P.bvh_node && P.scene_kind == SCN_TRI) {
-        if (P.bvh_stack <= 0 || P.bvh_stack > kBvhStack) return hipErrorInvalidValue;
-        // node indices below 2^16: 16-bit stack entries, half the LDS per thread
-        const bool small = P.bvh_nodes <= 0x10000;
-        const size_t ntop = std::min<size_t>((size_t)P.bvh_nodes, kBvhTopNodes);
-        const size_t lds = ntop * 4 * sizeof(f4) + (size_t)P.bvh_stack * kBlock * (small ? sizeof(uint16_t) : sizeof(uint32_t));
-        const bool nl1 = P.n_lights <= 1;
-        if (P.two_level) {
-            if (!P.deep || !P.deep_count) return hipErrorInvalidValue;
-            hipError_t e = zero_deep ? hipMemsetAsync(P.deep_count, 0, 3 * kMaxParts * sizeof(uint32_t), st)   // counts,
-                                     : hipSuccess;                                                        // fetch counters
-            if (e != hipSuccess) return e;
-            const size_t lds_a = (size_t)P.n_stri * 3 * sizeof(f4) + (size_t)P.n_sobj * (sizeof(DObjBox) + sizeof(DObjPlane));
-            if (P.sstep)
-                e = launch_trace_2a_coop(P, list, count, zero, blocks, st);
-            else if (nl1)
-                hipLaunchKernelGGL((k_trace_2a<1>), dim3(blocks), dim3(kBlock), lds_a, st, P, list, count, zero);
+    // every trace kernel has a one-light build and a kMaxLights one
+    return with_const<1, kMaxLights>(P.n_lights <= 1 ? 1 : kMaxLights, [&](auto nl) -> hipError_t {
+        constexpr int NL = decltype(nl)::value;
+        if (P.bvh_node && P.scene_kind == SCN_TRI) {
+            if (P.bvh_stack <= 0 || P.bvh_stack > kBvhStack) return hipErrorInvalidValue;
+            // node indices below 2^16: 16-bit stack entries, half the LDS per thread
+            const bool small = P.bvh_nodes <= 0x10000;
+            const size_t ntop = std::min<size_t>((size_t)P.bvh_nodes, kBvhTopNodes);
+            const size_t lds =
+                ntop * 4 * sizeof(f4) + (size_t)P.bvh_stack * kBlock * (small ? sizeof(uint16_t) : sizeof(uint32_t));
+            if (P.two_level) {
+                if (!P.deep || !P.deep_count) return hipErrorInvalidValue;
+                hipError_t e = zero_deep ? hipMemsetAsync(P.deep_count, 0, 3 * kMaxParts * sizeof(uint32_t), st)   // counts,
+                                         : hipSuccess;                                                        // fetch counters
+                if (e != hipSuccess) return e;
+                const size_t lds_a =
+                    (size_t)P.n_stri * 3 * sizeof(f4) + (size_t)P.n_sobj * (sizeof(DObjBox) + sizeof(DObjPlane));
+                if (P.sstep)
+                    e = launch_trace_2a_coop(P, list, count, zero, blocks, st);
+                else
+                    hipLaunchKernelGGL((k_trace_2a<NL>), dim3(blocks), dim3(kBlock), lds_a, st, P, list, count, zero);
+                if (e == hipSuccess) e = hipGetLastError();
+                return e;   // phase B: launch_trace_deep
+            }
+            if (small)
+                hipLaunchKernelGGL((k_trace_bvh<NL, uint16_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
             else
-                hipLaunchKernelGGL((k_trace_2a<kMaxLights>), dim3(blocks), dim3(kBlock), lds_a, st, P, list, count, zero);
-            if (e == hipSuccess) e = hipGetLastError();
-            return e;   // phase B: launch_trace_deep
+                hipLaunchKernelGGL((k_trace_bvh<NL, uint32_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
+            return hipGetLastError();
         }
-        if (small && nl1)
-            hipLaunchKernelGGL((k_trace_bvh<1, uint16_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
-        else if (small)
-            hipLaunchKernelGGL((k_trace_bvh<kMaxLights, uint16_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                               zero);
-        else if (nl1)
-            hipLaunchKernelGGL((k_trace_bvh<1, uint32_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
-        else
-            hipLaunchKernelGGL((k_trace_bvh<kMaxLights, uint32_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                               zero);
-        return hipGetLastError();
-    }
-    if (P.small_tri) {
-        const size_t lds = (size_t)P.n_tris * 3 * sizeof(f4) + (size_t)P.n_objs * sizeof(DObjBox);
-        if (P.n_lights <= 1)
-            hipLaunchKernelGGL((k_trace_small<1>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
-        else
-            hipLaunchKernelGGL((k_trace_small<kMaxLights>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                               zero);
-        return hipGetLastError();
-    }
-    switch (P.scene_kind) {
-        case SCN_TRI: return trace_nl<SCN_TRI>(P, list, count, zero, blocks, st);
-        case SCN_SPHERE: return trace_nl<SCN_SPHERE>(P, list, count, zero, blocks, st);
-        default: return trace_nl<SCN_MIXED>(P, list, count, zero, blocks, st);
-    }
-}
-
-template <int SCN>
-static hipError_t shade_i(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* out,
-                          uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st) {
-    if (P.integrator == XRT_INTEGRATOR_DIRECT)
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_DIRECT>), dim3(blocks), dim3(kBlock), 0, st, P, list,
-                           count, out, out_count, req_count);
-    else if (P.integrator == XRT_INTEGRATOR_VPT)
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_VPT>), dim3(blocks), dim3(kBlock), 0, st, P, list, count,
-                           out, out_count, req_count);
-    else if (P.integrator == XRT_INTEGRATOR_INDIRECT)
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_INDIRECT>), dim3(blocks), dim3(kBlock), 0, st, P, list, count,
-                           out, out_count, req_count);
-    else if (P.integrator == XRT_INTEGRATOR_NORMAL)
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_NORMAL>), dim3(blocks), dim3(kBlock), 0, st, P, list, count,
-                           out, out_count, req_count);
-    else if (P.integrator == XRT_INTEGRATOR_VPT_NEE)
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_VPT_NEE>), dim3(blocks), dim3(kBlock), 0, st, P, list, count,
-                           out, out_count, req_count);
-    else
-        hipLaunchKernelGGL((k_shade<SCN, XRT_INTEGRATOR_GI>), dim3(blocks), dim3(kBlock), 0, st, P, list, count,
-                           out, out_count, req_count);
-    return hipGetLastError();
+        if (P.small_tri) {
+            const size_t lds = (size_t)P.n_tris * 3 * sizeof(f4) + (size_t)P.n_objs * sizeof(DObjBox);
+            hipLaunchKernelGGL((k_trace_small<NL>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
+            return hipGetLastError();
+        }
+        return with_scene_kind(P.scene_kind, [&](auto scn) {
+            hipLaunchKernelGGL((k_trace<decltype(scn)::value, NL>), dim3(blocks), dim3(kBlock), 0, st, P, list, count, zero);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_shade(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* out,
                         uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st) {
-    switch (P.scene_kind) {
-        case SCN_TRI: return shade_i<SCN_TRI>(P, list, count, out, out_count, req_count, blocks, st);
-        case SCN_SPHERE: return shade_i<SCN_SPHERE>(P, list, count, out, out_count, req_count, blocks, st);
-        default: return shade_i<SCN_MIXED>(P, list, count, out, out_count, req_count, blocks, st);
-    }
+    return with_scene_kind(P.scene_kind, [&](auto scn) {
+        return with_integrator(P.integrator, [&](auto integ) {
+            hipLaunchKernelGGL((k_shade<decltype(scn)::value, decltype(integ)::value>), dim3(blocks), dim3(kBlock), 0, st,
+                               P, list, count, out, out_count, req_count);
+            return hipGetLastError();
+        });
+    });
 }
 
 size_t step_lds_bytes(const KParams& P) {
@@ -2404,52 +2364,6 @@ static size_t kstep_lds_bytes(const KParams& P, int bs) {
     return off ? off + (size_t)(bs / 64) * kMT * 4 : step_lds_bytes(P);
 }
 
-template <int SCN>
-static hipError_t step_i(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* out,
-                         uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
-                         uint64_t live, hipStream_t st) {
-    // Sphere-BVH scenes (C3) keep ~45 KB of BVH and spheres in LDS, so 256-thread blocks stop
-    // at 3 per CU (3 waves per SIMD); 512-thread blocks share one copy between 8 waves
-    // (4 waves per SIMD, the VGPR limit).  Same partitions, same results.
-    if (SCN == SCN_SPHERE && P.n_snode > 0 && kStepBlock512 && P.integrator == XRT_INTEGRATOR_DIRECT) {
-        // the grid must stay a multiple of n_part (part_iter: block b serves partition b % n_part
-        // and chunk b / n_part of gridDim / n_part chunks)
-        const uint32_t chunks = std::max(1u, blocks / P.n_part);
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_DIRECT, 512>), dim3(P.n_part * ((chunks + 1) / 2)), dim3(512),
-                           kstep_lds_bytes(P, 512), st, P, list, count, out, out_count, zero, req_count, visits);
-        return hipGetLastError();
-    }
-    const size_t lds = kstep_lds_bytes(P, kBlock);
-    if (P.integrator == XRT_INTEGRATOR_DIRECT)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_DIRECT>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    // volumetric walks with fewer live slots than 2 waves per SIMD hold (a row shard of a
-    // multi-GPU frame, a frame's tail): the 2-wave build, whose registers hold the walk without
-    // spilling (C5 shard 0 of 8: 43.9 -> 41.9 ms; a full frame stays at 4 waves per SIMD)
-    else if (P.integrator == XRT_INTEGRATOR_VPT && live < kVptLowLive)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_VPT, kBlock, 2>), dim3(blocks), dim3(kBlock), lds, st, P, list,
-                           count, out, out_count, zero, req_count, visits);
-    else if (P.integrator == XRT_INTEGRATOR_VPT_NEE && live < kVptLowLive)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_VPT_NEE, kBlock, 2>), dim3(blocks), dim3(kBlock), lds, st, P,
-                           list, count, out, out_count, zero, req_count, visits);
-    else if (P.integrator == XRT_INTEGRATOR_VPT)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_VPT>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    else if (P.integrator == XRT_INTEGRATOR_INDIRECT)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_INDIRECT>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    else if (P.integrator == XRT_INTEGRATOR_NORMAL)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_NORMAL>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    else if (P.integrator == XRT_INTEGRATOR_VPT_NEE)
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_VPT_NEE>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    else
-        hipLaunchKernelGGL((k_step<SCN, XRT_INTEGRATOR_GI>), dim3(blocks), dim3(kBlock), lds, st, P, list, count,
-                           out, out_count, zero, req_count, visits);
-    return hipGetLastError();
-}
-
 bool use_step_tri(const KParams& P) {
     return P.scene_kind == SCN_TRI && P.small_tri && P.n_objs <= kCoopMaxObjs &&
            (P.integrator == XRT_INTEGRATOR_GI || P.integrator == XRT_INTEGRATOR_DIRECT) && !exp_env("XRT_NO_COOP") &&
@@ -2458,24 +2372,47 @@ bool use_step_tri(const KParams& P) {
 
 hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count, uint32_t* out,
                        uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
-                       uint64_t live, hipStream_t st) {
+                       uint64_t live, bool tri, hipStream_t st) {
     if (!step_lds_bytes(P)) return hipErrorInvalidValue;
     if (P.n_part == 0 || blocks % P.n_part != 0) return hipErrorInvalidValue;   // part_iter's grid contract
-    if (use_step_tri(P)) {
+    if (tri) {   // use_step_tri: GI or Direct
         const size_t lds = ((step_layout(P).total + 15u) & ~15u) + (kBlock / 64) * sizeof(CoopWave);
-        if (P.integrator == XRT_INTEGRATOR_DIRECT)
-            hipLaunchKernelGGL((k_step_tri<XRT_INTEGRATOR_DIRECT>), dim3(blocks), dim3(kBlock), lds, st, dP, list,
-                               count, out, out_count, zero, req_count, visits);
-        else
-            hipLaunchKernelGGL((k_step_tri<XRT_INTEGRATOR_GI>), dim3(blocks), dim3(kBlock), lds, st, dP, list, count,
+        return with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {
+            hipLaunchKernelGGL((k_step_tri<decltype(integ)::value>), dim3(blocks), dim3(kBlock), lds, st, dP, list, count,
                                out, out_count, zero, req_count, visits);
-        return hipGetLastError();
+            return hipGetLastError();
+        });
     }
-    switch (P.scene_kind) {
-        case SCN_TRI: return step_i<SCN_TRI>(P, list, count, out, out_count, zero, req_count, visits, blocks, live, st);
-        case SCN_SPHERE: return step_i<SCN_SPHERE>(P, list, count, out, out_count, zero, req_count, visits, blocks, live, st);
-        default: return step_i<SCN_MIXED>(P, list, count, out, out_count, zero, req_count, visits, blocks, live, st);
-    }
+    return with_scene_kind(P.scene_kind, [&](auto scn) {
+        return with_integrator(P.integrator, [&](auto integ) {
+            constexpr int SCN = decltype(scn)::value, I = decltype(integ)::value;
+            // Sphere-BVH scenes (C3) keep ~45 KB of BVH and spheres in LDS, so 256-thread blocks stop
+            // at 3 per CU (3 waves per SIMD); 512-thread blocks share one copy between 8 waves
+            // (4 waves per SIMD, the VGPR limit).  Same partitions, same results.
+            if constexpr (I == XRT_INTEGRATOR_DIRECT)
+                if (SCN == SCN_SPHERE && P.n_snode > 0 && kStepBlock512) {
+                    // the grid must stay a multiple of n_part (part_iter: block b serves partition b % n_part
+                    // and chunk b / n_part of gridDim / n_part chunks)
+                    const uint32_t chunks = std::max(1u, blocks / P.n_part);
+                    hipLaunchKernelGGL((k_step<SCN, I, 512>), dim3(P.n_part * ((chunks + 1) / 2)), dim3(512),
+                                       kstep_lds_bytes(P, 512), st, P, list, count, out, out_count, zero, req_count, visits);
+                    return hipGetLastError();
+                }
+            const size_t lds = kstep_lds_bytes(P, kBlock);
+            // volumetric walks with fewer live slots than 2 waves per SIMD hold (a row shard of a
+            // multi-GPU frame, a frame's tail): the 2-wave build, whose registers hold the walk without
+            // spilling (C5 shard 0 of 8: 43.9 -> 41.9 ms; a full frame stays at 4 waves per SIMD)
+            if constexpr (I == XRT_INTEGRATOR_VPT || I == XRT_INTEGRATOR_VPT_NEE)
+                if (live < kVptLowLive) {
+                    hipLaunchKernelGGL((k_step<SCN, I, kBlock, 2>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out,
+                                       out_count, zero, req_count, visits);
+                    return hipGetLastError();
+                }
+            hipLaunchKernelGGL((k_step<SCN, I>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out, out_count, zero,
+                               req_count, visits);
+            return hipGetLastError();
+        });
+    });
 }
 
 // ------------------------------------------------------------------ ray queries ----
@@ -2553,12 +2490,10 @@ hipError_t launch_query(const KParams& P, const float* rays, const float* tmax, 
     if (e == hipSuccess) e = launch_trace(Q, list, count, zero, blocks, st);
     if (e == hipSuccess) e = launch_trace_deep(Q, st);
     if (e != hipSuccess) return e;
-    switch (P.scene_kind) {
-        case SCN_TRI: hipLaunchKernelGGL(k_query_out<SCN_TRI>, dim3(blocks), dim3(kBlock), 0, st, P, mode, out); break;
-        case SCN_SPHERE: hipLaunchKernelGGL(k_query_out<SCN_SPHERE>, dim3(blocks), dim3(kBlock), 0, st, P, mode, out); break;
-        default: hipLaunchKernelGGL(k_query_out<SCN_MIXED>, dim3(blocks), dim3(kBlock), 0, st, P, mode, out); break;
-    }
-    return hipGetLastError();
+    return with_scene_kind(P.scene_kind, [&](auto scn) {
+        hipLaunchKernelGGL(k_query_out<decltype(scn)::value>, dim3(blocks), dim3(kBlock), 0, st, P, mode, out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_finish(const KParams& P, hipStream_t st) {

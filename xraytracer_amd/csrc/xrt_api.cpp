@@ -54,9 +54,9 @@ struct xrt_ctx {
     DevBuf state, sample_k, depth, occ, rng_c, rng_g, ring, c_seg, c_shadow, c_rej, c_stall, lists, deep, camlist;
     DevBuf counts, stats, fb, scratch, kparams;
     size_t cap_fb = 0;
-    uint32_t* h_poll = nullptr;  // pinned
-    std::vector<hipEvent_t> events;
-    hipEvent_t poll_ev[8] = {};  // live-count polls of render_impl (created once)
+    uint32_t* h_poll = nullptr;  // pinned: LivePoll's 8 slots of kMaxParts counts
+    std::vector<hipEvent_t> events;   // LaunchTimer's pairs
+    hipEvent_t poll_ev[8] = {};  // LivePoll's events (created once)
     hipEvent_t wait_ev = nullptr;   // xrt_render_device_after: the caller stream's position
     // multi-GPU context (xrt_create_multi): one sub-context per device, each rendering an
     // interleaved row shard; the frame is assembled in subs[0]'s framebuffer
@@ -747,11 +747,13 @@ int xrt_set_medium_bricks(xrt_ctx* c, const xrt_medium_desc* m, const xrt_brick_
     return XRT_OK;
 }
 
-// wait: 0 = none (host output: the library owns the framebuffer), 1 = the whole device
-// (xrt_render_device), 2 = the caller's stream `wait_stream` (xrt_render_device_after)
-static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st,
-                       int wait = 0, hipStream_t wait_stream = nullptr) {
-    const auto t_start = std::chrono::steady_clock::now();
+}  // extern "C"
+
+// ------------------------------------------------------------------------ render ----
+// render_impl below is the sequence; each step is one of the pieces here.
+namespace {
+
+int check_render(xrt_ctx* c, const xrt_render_params* p) {
     if (!c || !p) return XRT_ERR_INVALID;
     if (!c->has_scene || !c->has_camera) return set_err(c, XRT_ERR_STATE, "upload a scene and set a camera first");
     if (p->width == 0 || p->height == 0 || p->shard_count == 0 || p->shard_index >= p->shard_count)
@@ -767,34 +769,31 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
         p->slots_per_wave != 32 && p->slots_per_wave != 64)
         return set_err(c, XRT_ERR_INVALID, "slots_per_wave must be 0, 4, 8, 16, 32 or 64");
     if (p->visits_per_launch > 128) return set_err(c, XRT_ERR_INVALID, "visits_per_launch must be 0..128");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (wait == 1) {
-        HIPCHK(c, hipDeviceSynchronize());
-    } else if (wait == 2) {
-        HIPCHK(c, hipEventRecord(c->wait_ev, wait_stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->wait_ev, 0));
-    }
-    const uint32_t rows = shard_rows(p->height, p->shard_index, p->shard_count);
-    const size_t n = (size_t)rows * p->width;
+    return XRT_OK;
+}
+
+// a shard that owns no rows (shard_index >= height): an all-zero framebuffer
+int render_empty_shard(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st,
+                       std::chrono::steady_clock::time_point t_start) {
     const size_t npix = (size_t)p->width * p->height;
     int rc;
-    if (n == 0) {
-        // a shard that owns no rows (shard_index >= height): an all-zero framebuffer
-        float* fb0 = d_out;
-        if (!fb0) {
-            if ((rc = ensure(c, c->fb, npix * 3 * sizeof(float)))) return rc;
-            fb0 = as<float>(c->fb);
-        }
-        if (p->flags & XRT_FLAG_ACCUMULATE) return XRT_OK;   // nothing owned, nothing touched
-        HIPCHK(c, hipMemsetAsync(fb0, 0, npix * 3 * sizeof(float), c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h_out) HIPCHK(c, hipMemcpy(h_out, fb0, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (st) {
-            std::memset(st, 0, sizeof(*st));
-            st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        }
-        return XRT_OK;
+    if (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float)))) return rc;
+    float* fb0 = d_out ? d_out : as<float>(c->fb);
+    if (p->flags & XRT_FLAG_ACCUMULATE) return XRT_OK;   // nothing owned, nothing touched
+    HIPCHK(c, hipMemsetAsync(fb0, 0, npix * 3 * sizeof(float), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h_out) HIPCHK(c, hipMemcpy(h_out, fb0, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (st) {
+        std::memset(st, 0, sizeof(*st));
+        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
+    return XRT_OK;
+}
+
+// per-slot path state for n slots (buffers only grow), the live-list counters, the stats
+// words and the device copy of KParams
+int grow_slots(xrt_ctx* c, size_t n) {
+    int rc;
     if (n > c->cap_slots) {
         const size_t L = kMaxLights;
         if ((rc = ensure(c, c->ray_o, n * 16)) || (rc = ensure(c, c->ray_d, n * 16)) || (rc = ensure(c, c->thr, n * 16)) ||
@@ -812,11 +811,25 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
         c->cap_slots = n;
     }
     if ((rc = ensure(c, c->counts, 5 * kMaxParts * 4)) || (rc = ensure(c, c->stats, 512))) return rc;
-    float* fb = d_out;
-    if (!fb) {
-        if ((rc = ensure(c, c->fb, npix * 3 * sizeof(float)))) return rc;
-        fb = as<float>(c->fb);
-    }
+    return ensure(c, c->kparams, sizeof(KParams));
+}
+
+void bind_slots(xrt_ctx* c, KParams& P) {
+    P.ray_o = as<f4>(c->ray_o), P.ray_d = as<f4>(c->ray_d), P.thr = as<f4>(c->thr), P.rad = as<f4>(c->rad);
+    P.thr_prev = as<f4>(c->thr_prev), P.hit = as<f4>(c->hit), P.hit2 = as<f4>(c->hit2), P.hit3 = as<f4>(c->hit3);
+    P.sh_o = as<f4>(c->sh_o), P.sh_d = as<f4>(c->sh_d), P.sh_c = as<f4>(c->sh_c);
+    P.med = as<f4>(c->med), P.med2 = as<f4>(c->med2), P.nee = as<f4>(c->nee);
+    P.state = as<uint32_t>(c->state), P.sample_k = as<uint32_t>(c->sample_k), P.depth = as<uint32_t>(c->depth);
+    P.occ = as<uint32_t>(c->occ), P.rng_c = as<uint32_t>(c->rng_c), P.rng_g = as<uint32_t>(c->rng_g);
+    P.ring = as<uint32_t>(c->ring);
+    P.c_seg = as<uint32_t>(c->c_seg), P.c_shadow = as<uint32_t>(c->c_shadow), P.c_rej = as<uint32_t>(c->c_rej);
+    P.c_stall = as<uint32_t>(c->c_stall);
+    P.stats = as<unsigned long long>(c->stats);
+}
+
+// the scene's parameters with this render's image, shard and flags; the schedule's share
+// (partitions, rng_keep, queues, lists) follows from plan_render
+KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* fb) {
     KParams P = c->base;
     P.integrator = p->integrator;
     P.max_depth = p->max_depth, P.width = p->width, P.height = p->height, P.spp = p->spp;
@@ -827,272 +840,294 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
     P.spw_req = p->slots_per_wave, P.rflags = p->flags;
     // two-level traces: the BVH walk takes four lanes per queued ray (k_trace_deep4q, every
     // size: its lanes keep their own best hits) unless the caller asks for one
-    {
-        const char* dq = exp_env("XRT_DEEP_QUAD");
-        P.deep_quad = dq ? std::atoi(dq) : (p->flags & XRT_FLAG_DEEP_SINGLE) ? 0 : 1;
-    }
-    // Schedule, decided once (the partition count below depends on it): the fused k_step
-    // (scene resident in LDS, kStepVisits path segments per slot per launch, in-kernel
-    // compaction and refill requests) when the scene fits, in its merged-trace form for small
-    // triangle scenes; else the multi-pass wavefront (k_shade, then k_trace streaming the
-    // scene through LDS tiles; k_shade refills its slots' rings in-line).
-    // Two-level scenes (C4) take the merged kernel with the wave's own BVH walk.
-    const bool bvh = !(p->flags & (XRT_FLAG_WAVEFRONT | XRT_FLAG_NO_MERGED)) && use_step_bvh(P);
-    // Direct / Normal over an LDS-resident scene: pixel-parallel sample chains (pixel.hip) —
-    // one k_pixel launch between k_seed and k_finish, no live lists, no refill launch
-    const bool pixel = !bvh && !(p->flags & (XRT_FLAG_WAVEFRONT | XRT_FLAG_NO_PIXEL)) && use_pixel(P);
-    const bool fused = bvh || (!(p->flags & XRT_FLAG_WAVEFRONT) && step_lds_bytes(P) != 0);
-    const bool merged = bvh || (fused && !(p->flags & XRT_FLAG_NO_MERGED) && use_step_merged(P));
-    // speculative sample starts for the merged schedule's 16-slot launches (spec.hip)
-    const bool spec = merged && !bvh && !(p->flags & XRT_FLAG_NO_SPEC) && use_step_spec(P);
+    const char* dq = exp_env("XRT_DEEP_QUAD");
+    P.deep_quad = dq ? std::atoi(dq) : (p->flags & XRT_FLAG_DEEP_SINGLE) ? 0 : 1;
+    bind_slots(c, P);
+    P.fb = fb;
+    P.camlist = nullptr;
+    return P;
+}
+
+// The schedule of one render, decided once (plan_render) before anything is launched: the
+// loops, the launchers' arguments and xrt_stats all read it from here.
+struct RenderPlan {
+    int schedule;       // XRT_SCHED_*
+    bool volumetric;    // VPT / VPT-NEE: unbounded walks
+    // pixel: one k_pixel launch between k_seed and k_finish, no live lists, no refill, no
+    // loop (fused and merged are then only what sized the partitions).  Otherwise fused: the
+    // k_step loop (else k_shade + k_trace); merged: its k_step_merged form; two_level: that
+    // kernel with the wave's own BVH walk; step_tri: k_step_tri in place of k_step; spec:
+    // k_step_spec in the merged schedule's group layouts, which needs the camera lists
+    bool pixel, fused, merged, two_level, step_tri, spec, camlist;
+    uint32_t n_part, part_cap;                     // live-list partitions
+    uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
+    uint64_t poll_every, ahead;                    // LivePoll cadence
+    uint64_t cap_iters;                            // loop iterations at most
+};
+
+RenderPlan plan_render(const KParams& P, const xrt_render_params* p) {
+    RenderPlan R{};
+    const size_t n = P.n_slots;
+    R.volumetric = p->integrator == XRT_INTEGRATOR_VPT || p->integrator == XRT_INTEGRATOR_VPT_NEE;
+    // The fused k_step (scene resident in LDS, step_visits path segments per slot per launch,
+    // in-kernel compaction and ring refills) when the scene fits, in its merged-trace form for
+    // small triangle scenes; else the multi-pass wavefront (k_shade, then k_trace streaming the
+    // scene through LDS tiles).  Two-level scenes (C4) take the merged kernel with the wave's
+    // own BVH walk.  Direct / Normal over an LDS-resident scene: pixel-parallel sample chains
+    // (pixel.hip).  Speculative sample starts serve the merged schedule's 16-slot and tail
+    // launches (spec.hip).
+    R.two_level = !(p->flags & (XRT_FLAG_WAVEFRONT | XRT_FLAG_NO_MERGED)) && use_step_bvh(P);
+    R.pixel = !R.two_level && !(p->flags & (XRT_FLAG_WAVEFRONT | XRT_FLAG_NO_PIXEL)) && use_pixel(P);
+    R.fused = R.two_level || (!(p->flags & XRT_FLAG_WAVEFRONT) && step_lds_bytes(P) != 0);
+    R.merged = R.two_level || (R.fused && !(p->flags & XRT_FLAG_NO_MERGED) && use_step_merged(P));
+    R.step_tri = R.fused && !R.merged && use_step_tri(P);
+    R.spec = R.merged && !R.two_level && !(p->flags & XRT_FLAG_NO_SPEC) && use_step_spec(P);
+    R.camlist = R.spec && !exp_env("XRT_NO_CAMLIST");
+    R.schedule = R.pixel       ? XRT_SCHED_PIXEL
+                 : !R.fused    ? XRT_SCHED_WAVEFRONT
+                 : R.two_level ? XRT_SCHED_STEP_BVH
+                 : R.merged    ? XRT_SCHED_STEP_MERGED
+                 : R.step_tri  ? XRT_SCHED_STEP_TRI
+                               : XRT_SCHED_STEP;
     // live-list partitions (a multiple of the 8 XCDs): every wave appends to its partition's
     // counters once per launch, so more partitions mean less atomic contention (64 -> 256:
     // C4 -14%, C2 -4.5%).  The merged schedule (64 segments per launch) is fastest with
     // >= 2048 slots per partition (at most 256), the per-segment ones with >= 512 (at most
     // kMaxParts): C3 -8%, C4 -4% over 256
-    {
-        const bool merged_sched = merged;
-        const size_t cap = merged_sched ? 256 : kMaxParts, per = merged_sched ? 2048 : kPartMinSlots;
-        uint32_t np = (uint32_t)std::min<size_t>(cap, std::max<size_t>(1, n / per));
-        if (np >= 8) np &= ~7u;
-        P.n_part = np;
-        P.part_cap = (uint32_t)((n + np - 1) / np);
-    }
-    const size_t lcap = (size_t)P.n_part * P.part_cap;
-    P.ray_o = as<f4>(c->ray_o), P.ray_d = as<f4>(c->ray_d), P.thr = as<f4>(c->thr), P.rad = as<f4>(c->rad);
-    P.thr_prev = as<f4>(c->thr_prev), P.hit = as<f4>(c->hit), P.hit2 = as<f4>(c->hit2), P.hit3 = as<f4>(c->hit3);
-    P.sh_o = as<f4>(c->sh_o), P.sh_d = as<f4>(c->sh_d), P.sh_c = as<f4>(c->sh_c);
-    P.med = as<f4>(c->med), P.med2 = as<f4>(c->med2), P.nee = as<f4>(c->nee);
-    P.state = as<uint32_t>(c->state), P.sample_k = as<uint32_t>(c->sample_k), P.depth = as<uint32_t>(c->depth);
-    P.occ = as<uint32_t>(c->occ), P.rng_c = as<uint32_t>(c->rng_c), P.rng_g = as<uint32_t>(c->rng_g);
-    P.ring = as<uint32_t>(c->ring);
-    P.c_seg = as<uint32_t>(c->c_seg), P.c_shadow = as<uint32_t>(c->c_shadow), P.c_rej = as<uint32_t>(c->c_rej);
-    P.c_stall = as<uint32_t>(c->c_stall);
-    P.fb = fb;
-    P.stats = as<unsigned long long>(c->stats);
-    if ((rc = setup_deep(c, P))) return rc;
-
-    uint32_t* lists[2] = {as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap};
-    P.req = as<uint32_t>(c->lists) + 2 * lcap;
-    // counter arrays of kMaxParts words: live[0..2] (rotating), then refill[0..1]
-    uint32_t* cbase = as<uint32_t>(c->counts);
-    auto counts_at = [&](uint64_t j) { return cbase + (size_t)j * kMaxParts; };
-    uint32_t* req_counts = cbase + 3 * kMaxParts;
-    const bool timing = (p->flags & XRT_FLAG_TIMING) != 0;
-    xrt_stats S;
-    std::memset(&S, 0, sizeof(S));
-    S.path_slots = n;
-    S.samples = (uint64_t)n * p->spp;
-    std::vector<std::pair<int, size_t>> ev_use;   // (kernel id, first event index)
-    size_t ev_next = 0;
-    auto ev_pair = [&](int kid) -> size_t {
-        while (c->events.size() < ev_next + 2) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return (size_t)-1;
-            c->events.push_back(e);
-        }
-        const size_t i = ev_next;
-        ev_next += 2;
-        ev_use.push_back({kid, i});
-        return i;
-    };
-    auto launch = [&](int kid, auto&& fn) -> hipError_t {
-        size_t e = timing ? ev_pair(kid) : (size_t)-1;
-        if (e != (size_t)-1) (void)hipEventRecord(c->events[e], c->stream);
-        hipError_t err = fn();
-        if (e != (size_t)-1) (void)hipEventRecord(c->events[e + 1], c->stream);
-        S.launches[kid]++;
-        return err;
-    };
-
-    if (!(p->flags & XRT_FLAG_ACCUMULATE))
-        HIPCHK(c, hipMemsetAsync(fb, 0, npix * 3 * sizeof(float), c->stream));
-    else if (h_out)   // the caller's Image is the accumulator (Src/renderer.cpp:75)
-        HIPCHK(c, hipMemcpyAsync(fb, h_out, npix * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(P.stats, 0, 512, c->stream));
-    HIPCHK(c, launch(XRT_K_SEED, [&] { return launch_seed(P, lists[0], counts_at(0), counts_at(1), req_counts, c->stream); }));
-    // the pixels' camera-ray triangle lists (small triangle scenes on the merged schedule:
-    // k_step_spec's candidates, and with XRT_MERGED_CAMLIST the merged kernel's camera rays),
-    // once per render, timed with the seeding; built before the first launch that reads them
-    P.camlist = nullptr;
-    bool camlist_pending = false;
-    if (merged && !bvh && P.n_tris <= 64 && !exp_env("XRT_NO_CAMLIST")) {
-        if ((rc = ensure(c, c->camlist, n * sizeof(uint4)))) return rc;
-        P.camlist = as<uint4>(c->camlist);
-        camlist_pending = true;
-    }
-    auto build_camlist = [&]() -> hipError_t {
-        camlist_pending = false;
-        return launch(XRT_K_SEED, [&] { return launch_camlist(P, c->stream); });
-    };
-    if (camlist_pending && XRT_MERGED_CAMLIST) HIPCHK(c, build_camlist());
-    if (pixel) {
-        // every pixel of the shard in one persistent launch; the pixel counter is a stats word
-        // (zeroed with them above)
-        uint32_t* work = reinterpret_cast<uint32_t*>(P.stats + kStatsWork);
-        hipError_t e = launch(XRT_K_STEP, [&] { return launch_pixel(P, work, c->stream); });
-        if (e != hipSuccess) return hip_err(c, e, "k_pixel");
-    }
-    // refill epochs: shading launches of epoch e append to req_counts[e & 1]; k_refill(e)
-    // consumes it and clears req_counts[(e + 1) & 1] for epoch e + 1.  Epoch 0 is the
-    // first twist of every slot, requested by k_seed.
-    uint64_t epoch = 0;
-    bool merged_refill = false;   // set once the merged schedule is chosen (below)
-    auto refill = [&]() -> hipError_t {
-        const int a = (int)(epoch & 1), b = a ^ 1;
-        ++epoch;
-        return launch(XRT_K_REFILL, [&] {
-            if (merged_refill)
-                return launch_refill_merged(P, req_counts + a * kMaxParts, req_counts + b * kMaxParts, c->stream);
-            return launch_refill(P, req_counts + a * kMaxParts, req_counts + b * kMaxParts, c->stream);
-        });
-    };
-    if (!pixel) HIPCHK(c, refill());
-
-    const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // one entry per thread
-    // GI/Direct: at most max_depth + 1 shade passes per sample; VPT walks are unbounded
-    // (null collisions, suspensions), so only the live-slot poll ends the loop there.
-    const uint64_t cap_iters = volumetric ? (uint64_t)p->spp * 100000ull + 1000000ull
-                                          : (uint64_t)p->spp * (p->max_depth + 2) + 16;
-    // asynchronous termination polling: every kPoll iterations copy the live-slot count to
-    // pinned memory; block on a poll only when the host runs kAhead iterations ahead.
-    constexpr uint64_t kPoll = 16, kAhead = 64;
-    struct Poll { uint64_t it; hipEvent_t ev; int slot; };
-    std::vector<Poll> polls;
-    hipEvent_t* poll_ev = c->poll_ev;
-    uint64_t it = 0;
-    int poll_slot = 0;
-    bool done = pixel;   // the pixel schedule has no step loop
-    // k_step rotates three live counters: round i reads counts[i%3], appends to
-    // counts[(i+1)%3] and clears counts[(i+2)%3] for round i+1 (every step kernel twists its
-    // slots' rings in-line at the end of the launch: no k_refill after the seeding one).
-    // segments per slot per step launch: kMergedVisits / kStepVisits unless the caller
-    // sets visits_per_launch (results do not depend on it)
-    const uint32_t merged_visits =
-        merged ? std::min<uint32_t>(kMergedVisits, (kMT - step_merged_draws(P)) / step_merged_draws(P)) : 0;
+    const size_t cap = R.merged ? 256 : kMaxParts, per = R.merged ? 2048 : kPartMinSlots;
+    R.n_part = (uint32_t)std::min<size_t>(cap, std::max<size_t>(1, n / per));
+    if (R.n_part >= 8) R.n_part &= ~7u;
+    R.part_cap = (uint32_t)((n + R.n_part - 1) / R.n_part);
+    // segments per slot per step launch: kMergedVisits / kStepVisits unless the caller sets
+    // visits_per_launch (results do not depend on it)
+    const uint32_t draws = step_merged_draws(P);
     const char* ev = exp_env("XRT_VISITS");   // experiment builds only
-    const uint32_t step_visits = ev                    ? (uint32_t)std::atoi(ev)
-                                 : p->visits_per_launch ? p->visits_per_launch
-                                 : merged               ? merged_visits
-                                 : (volumetric && kVptEvents) ? kVptEventVisits
-                                                        : kStepVisits;
-    merged_refill = merged;
+    R.step_visits = ev                             ? (uint32_t)std::atoi(ev)
+                    : p->visits_per_launch          ? p->visits_per_launch
+                    : R.merged                      ? std::min<uint32_t>(kMergedVisits, (kMT - draws) / draws)
+                    : (R.volumetric && kVptEvents) ? kVptEventVisits
+                                                    : kStepVisits;
+    // k_step_spec reads up to kSpecDraws words past the cursor per visit: fewer visits per launch
+    // (with XRT_SPEC_TWIST it twists in-loop instead: XRT_SPEC_VISITS visits unless the caller sets them)
+    R.spec_visits = !R.spec          ? 0
+                    : XRT_SPEC_TWIST ? ((ev || p->visits_per_launch) ? R.step_visits : XRT_SPEC_VISITS)
+                                     : std::min<uint32_t>(R.step_visits, (kMT - kSpecDraws) / kSpecDraws);
     // a slot's ring is twisted at the end of a launch when fewer words are left than the next
     // launch can draw: the merged kernel draws at most step_merged_draws per segment and
     // checks it; k_step / k_step_tri check kRngVisit per visit
-    // k_step_spec reads up to kSpecDraws words past the cursor per visit: fewer visits per launch
-    // (with XRT_SPEC_TWIST it twists in-loop instead: XRT_SPEC_VISITS visits unless the caller sets them)
-    const uint32_t spec_visits = !spec ? 0
-                                 : XRT_SPEC_TWIST ? ((ev || p->visits_per_launch) ? step_visits : XRT_SPEC_VISITS)
-                                                  : std::min<uint32_t>(step_visits, (kMT - kSpecDraws) / kSpecDraws);
-    P.rng_keep = spec && !XRT_SPEC_TWIST
-                     ? std::max(step_visits * step_merged_draws(P) + step_merged_draws(P), spec_visits * kSpecDraws + kSpecDraws)
-                 : merged                      ? step_visits * step_merged_draws(P) + step_merged_draws(P)
-                 : (volumetric && kVptEvents) ? step_visits * kVptEventDraws + kRngVisit
-                                              : step_visits * kVisitDraws + kRngVisit;
-    if (!pixel && P.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
-    // device copy of the (now final) parameters for kernels that read them from memory
-    if ((rc = ensure(c, c->kparams, sizeof(KParams)))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->kparams.p, &P, sizeof(KParams), hipMemcpyHostToDevice, c->stream));
-    const KParams* dP = as<KParams>(c->kparams);
+    R.rng_keep = R.spec && !XRT_SPEC_TWIST
+                     ? std::max(R.step_visits * draws + draws, R.spec_visits * kSpecDraws + kSpecDraws)
+                 : R.merged                     ? R.step_visits * draws + draws
+                 : (R.volumetric && kVptEvents) ? R.step_visits * kVptEventDraws + kRngVisit
+                                                : R.step_visits * kVisitDraws + kRngVisit;
     // the merged schedule polls every launch and runs at most 3 launches ahead of the last
-    // retired poll, so its per-launch layout (below) follows the live count closely
-    const uint64_t poll_every = merged ? 1 : fused ? 4 : kPoll, ahead = merged ? 3 : fused ? 16 : kAhead;
-    // merged schedule: the slots-per-wave layout is chosen from the shard's slot count (full
-    // waves for a whole frame, 2 or 4 lanes per slot for small pixel shards); switching it
-    // as the live count drops measured slower.  Every layout gives identical
-    // results.
-    // The merged schedule re-chooses the layout every launch from the live count of the last
-    // retired poll (an upper bound: paths only finish), so a frame's tail, where few slots
-    // remain, runs with more lanes per slot, and sizes the grid by the fullest
-    // partition's live count instead of its capacity.  Results never depend on the layout.
-    uint64_t live_hint = n;
-    uint32_t live_part_max = P.part_cap;
-    std::vector<uint64_t> launch_live;   // the live hint each step launch was sized with
-    size_t step_idx = 0;
-    for (; it < cap_iters && !done; ++it) {
-        const int cur = (int)(it & 1), nxt = cur ^ 1;
-        uint32_t* live = nullptr;
-        if (fused) {
-            const int ci = (int)(it % 3), co = (int)((it + 1) % 3), cz = (int)((it + 2) % 3);
-            live = counts_at(co);
-            launch_live.push_back(live_hint);
-            if (merged) {
-                const uint32_t spw = step_merged_spw(P, live_hint);
-                S.layout_launches[spw == 64 ? 0 : spw == 32 ? 1 : spw == 16 ? 2 : spw == 8 ? 3 : 4]++;
-            }
-            // speculative starts in the group layouts (4 lanes per slot; 16 in the tail; 8 when forced)
-            const uint32_t spw_now = merged ? step_merged_spw(P, live_hint) : 0;
-            const bool spec_now = spec && P.camlist && (spw_now == 16 || spw_now == 8 || (XRT_SPEC_TAIL && spw_now == 4)) &&
-                                  step_merged_group(P, spw_now) * spw_now == 64;
-            if (spec_now) S.spec_launches++;
-            if (spec_now && camlist_pending) HIPCHK(c, build_camlist());
-            hipError_t e = launch(XRT_K_STEP, [&] {
-                if (spec_now)
-                    return launch_step_spec(P, dP, lists[cur], counts_at(ci), lists[nxt], counts_at(co), counts_at(cz),
-                                            spec_visits, live_part_max, spw_now, c->stream);
-                if (merged)
-                    return launch_step_merged(P, dP, c->step_objs, lists[cur], counts_at(ci), lists[nxt],
-                                              counts_at(co), counts_at(cz), req_counts + (epoch & 1) * kMaxParts,
-                                              step_visits, live_hint, live_part_max, c->stream);
-                return launch_step(P, dP, lists[cur], counts_at(ci), lists[nxt], counts_at(co), counts_at(cz),
-                                   req_counts + (epoch & 1) * kMaxParts, step_visits, blocks, live_hint, c->stream);
-            });
-            if (e != hipSuccess) return hip_err(c, e, "k_step");
-            // both step kernels refill their slots' rings themselves (wave_refill)
-        } else {
-            live = counts_at(nxt);
-            hipError_t e = launch(XRT_K_SHADE, [&] {
-                return launch_shade(P, lists[cur], counts_at(cur), lists[nxt], counts_at(nxt),
-                                    req_counts + (epoch & 1) * kMaxParts, blocks, c->stream);
-            });
-            if (e != hipSuccess) return hip_err(c, e, "k_shade");
-            e = launch(XRT_K_TRACE, [&] {
-                return launch_trace(P, lists[nxt], counts_at(nxt), counts_at(cur), blocks, c->stream, false);
-            });
-            if (e != hipSuccess) return hip_err(c, e, "k_trace");
-            if (P.two_level && P.bvh_node && P.scene_kind == SCN_TRI) {
-                e = launch(XRT_K_DEEP, [&] { return launch_trace_deep(P, c->stream); });
-                if (e != hipSuccess) return hip_err(c, e, "k_trace_deep4");
-            }
-            // no k_refill: k_shade twists its slots' rings itself (wave_refill)
+    // retired poll, so the layout and grid it chooses per launch follow the live count closely
+    R.poll_every = R.merged ? 1 : R.fused ? 4 : 16;
+    R.ahead = R.merged ? 3 : R.fused ? 16 : 64;
+    // GI/Direct: at most max_depth + 1 shade passes per sample; VPT walks are unbounded
+    // (null collisions, suspensions), so only the live-slot poll ends the loop there.
+    R.cap_iters = R.volumetric ? (uint64_t)p->spp * 100000ull + 1000000ull
+                               : (uint64_t)p->spp * (p->max_depth + 2) + 16;
+    return R;
+}
+
+// A render's live lists: two slot lists of n_part * part_cap entries that the launches
+// ping-pong between (KParams::req, the refill request list, lies behind them), and counter
+// arrays of kMaxParts words: three live counters that the loops rotate, then two request
+// counters.  k_seed asks for every slot's first ring twist in req(0); the seeding refill
+// consumes it and clears req(1), which every later launch is handed (they twist in-line).
+struct LiveLists {
+    uint32_t* list[2];
+    uint32_t* cbase;
+    uint32_t* counts(uint64_t j) const { return cbase + (size_t)j * kMaxParts; }
+    uint32_t* req(int j) const { return counts(3 + j); }
+};
+
+// Counts every launch into xrt_stats::launches and, with XRT_FLAG_TIMING, puts a pair of the
+// context's events round it; read_out, once the stream is synchronised, turns the pairs into
+// kernel_ms (and the per-launch trace of experiment builds).
+struct LaunchTimer {
+    xrt_ctx* c;
+    xrt_stats& S;
+    bool timing;
+    std::vector<int> kids;             // launch q: kernel id (its events: 2q, 2q + 1)
+    std::vector<uint64_t> step_live;   // fused loop: the live hint each step launch was sized with
+
+    template <typename F>
+    hipError_t launch(int kid, F&& fn) {
+        const size_t e = 2 * kids.size();
+        bool timed = timing;
+        while (timed && c->events.size() < e + 2) {   // created on first use, kept by the context
+            hipEvent_t ev;
+            if ((timed = hipEventCreate(&ev) == hipSuccess)) c->events.push_back(ev);
         }
-        if (it % poll_every == poll_every - 1) {
-            const int ps = poll_slot++ % 8;
-            HIPCHK(c, hipMemcpyAsync(c->h_poll + ps * kMaxParts, live, P.n_part * 4, hipMemcpyDeviceToHost,
-                                     c->stream));
-            HIPCHK(c, hipEventRecord(poll_ev[ps], c->stream));
-            polls.push_back({it, poll_ev[ps], ps});
+        if (timed) kids.push_back(kid);
+        if (timed) (void)hipEventRecord(c->events[e], c->stream);
+        const hipError_t err = fn();
+        if (timed) (void)hipEventRecord(c->events[e + 1], c->stream);
+        S.launches[kid]++;
+        return err;
+    }
+    void read_out() {
+        if (!timing) return;
+        const bool trace = exp_env("XRT_TRACE_LAUNCHES") != nullptr;   // experiments: per-launch times
+        size_t step_idx = 0;
+        for (size_t q = 0; q < kids.size(); ++q) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, c->events[2 * q], c->events[2 * q + 1]) == hipSuccess) S.kernel_ms[kids[q]] += ms;
+            if (trace) {
+                float gap = 0.0f;
+                if (q) (void)hipEventElapsedTime(&gap, c->events[2 * q - 1], c->events[2 * q]);
+                std::fprintf(stderr, "[xrt] launch %zu kernel %d %.3f ms (gap %.3f)%s", q, kids[q], ms, gap,
+                             kids[q] == XRT_K_STEP && q < step_live.size() + 2 ? "" : "\n");
+                if (kids[q] == XRT_K_STEP) {
+                    const size_t si = step_idx++;
+                    std::fprintf(stderr, " live %llu\n", si < step_live.size() ? (unsigned long long)step_live[si] : 0ull);
+                }
+            }
         }
-        // retire polls: non-blocking when possible, blocking when too far ahead
-        while (!polls.empty()) {
-            Poll& q = polls.front();
+    }
+};
+
+// Asynchronous termination polling.  Every `every` loop iterations the live counters that
+// iteration wrote are copied into one of the context's 8 pinned slots, with an event behind
+// the copy.  Polls are retired in order: without blocking once their event has fired, by
+// waiting once the host is `ahead` iterations past one.  Retired polls give `done` (no live
+// slot left) and the live counts the merged schedule chooses its layout and grid by (upper
+// bounds: paths only finish).
+struct LivePoll {
+    xrt_ctx* c;
+    uint32_t n_part;
+    uint64_t every, ahead;
+    bool part_max;            // follow the fullest partition too (merged schedule, layout not forced)
+    uint64_t live_hint;       // live slots at the last retired poll
+    uint32_t live_part_max;   // ... in the fullest partition
+    bool done = false;
+    struct Pending { uint64_t it; int slot; };
+    std::vector<Pending> pending;
+    int issued = 0;
+
+    // after iteration `it`, whose launches left the live counts in `live` (device)
+    int after(uint64_t it, const uint32_t* live) {
+        if (it % every == every - 1) {
+            const int ps = issued++ % 8;
+            HIPCHK(c, hipMemcpyAsync(c->h_poll + ps * kMaxParts, live, n_part * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventRecord(c->poll_ev[ps], c->stream));
+            pending.push_back({it, ps});
+        }
+        while (!pending.empty()) {
+            const Pending q = pending.front();
             const bool must_wait = it - q.it >= ahead;
-            if (!must_wait && hipEventQuery(q.ev) != hipSuccess) break;
-            HIPCHK(c, hipEventSynchronize(q.ev));
+            if (!must_wait && hipEventQuery(c->poll_ev[q.slot]) != hipSuccess) break;
+            HIPCHK(c, hipEventSynchronize(c->poll_ev[q.slot]));
+            const uint32_t* h = c->h_poll + q.slot * kMaxParts;
             uint64_t alive = 0;
             uint32_t pmax = 0;
-            for (uint32_t k = 0; k < P.n_part; ++k)
-                alive += c->h_poll[q.slot * kMaxParts + k], pmax = std::max(pmax, c->h_poll[q.slot * kMaxParts + k]);
+            for (uint32_t k = 0; k < n_part; ++k) alive += h[k], pmax = std::max(pmax, h[k]);
             if (alive == 0) done = true;
             if (alive < live_hint) {
                 live_hint = alive;
-                if (merged && !P.spw_req) live_part_max = std::max(1u, pmax);
+                if (part_max) live_part_max = std::max(1u, pmax);
             }
-            polls.erase(polls.begin());
+            pending.erase(pending.begin());
             if (done) break;
         }
+        return XRT_OK;
     }
-    S.iterations = it;
-    HIPCHK(c, launch(XRT_K_FINISH, [&] { return launch_finish(P, c->stream); }));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!done) {
-        // the iteration cap was reached without observing an empty list: verify
-        uint32_t left[kMaxParts] = {0};
-        HIPCHK(c, hipMemcpy(left, counts_at(fused ? it % 3 : it & 1), P.n_part * 4, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < P.n_part; ++k)
-            if (left[k] != 0) return set_err(c, XRT_ERR_HIP, "iteration cap reached with live paths");
+};
+
+// k_seed, then the slots' first samples: k_pixel renders them outright; every other schedule
+// twists each slot's ring (the refill k_seed requested).  Last, the device copy of the
+// parameters for the kernels that read them from memory.
+int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T) {
+    HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_seed(P, L.list[0], L.counts(0), L.counts(1), L.req(0), c->stream); }));
+    if (R.pixel) {
+        // every pixel of the shard in one persistent launch; the pixel counter is a stats word
+        // (zeroed with them)
+        uint32_t* work = reinterpret_cast<uint32_t*>(P.stats + kStatsWork);
+        const hipError_t e = T.launch(XRT_K_STEP, [&] { return launch_pixel(P, work, c->stream); });
+        if (e != hipSuccess) return hip_err(c, e, "k_pixel");
+    } else {
+        HIPCHK(c, T.launch(XRT_K_REFILL, [&] {
+            return R.merged ? launch_refill_merged(P, L.req(0), L.req(1), c->stream)
+                            : launch_refill(P, L.req(0), L.req(1), c->stream);
+        }));
     }
+    HIPCHK(c, hipMemcpyAsync(c->kparams.p, &P, sizeof(KParams), hipMemcpyHostToDevice, c->stream));
+    return XRT_OK;
+}
+
+// The fused schedules' loop: one step launch per iteration over three rotating counter
+// arrays — round i reads counts(i % 3), appends to counts((i + 1) % 3) and clears
+// counts((i + 2) % 3) for round i + 1.  Every step kernel twists its slots' rings in-line at
+// the end of the launch.  The merged schedule chooses its slots-per-wave layout every launch
+// from the live count of the last retired poll, so a frame's tail, where few slots remain,
+// runs with more lanes per slot, and sizes the grid by the fullest partition's
+// live count instead of its capacity.  Results never depend on the layout.
+int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, LivePoll& poll,
+              uint64_t& it) {
+    const KParams* dP = as<KParams>(c->kparams);
+    const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // k_step, k_step_tri: one entry per thread
+    bool camlist_pending = R.camlist;   // built before the first launch that reads them, timed with the seeding
+    for (it = 0; it < R.cap_iters && !poll.done; ++it) {
+        const uint32_t *list = L.list[it & 1], *ci = L.counts(it % 3);
+        uint32_t *out = L.list[~it & 1], *co = L.counts((it + 1) % 3), *cz = L.counts((it + 2) % 3);
+        T.step_live.push_back(poll.live_hint);
+        const uint32_t spw = R.merged ? step_merged_spw(P, poll.live_hint) : 0;
+        if (R.merged) T.S.layout_launches[spw == 64 ? 0 : spw == 32 ? 1 : spw == 16 ? 2 : spw == 8 ? 3 : 4]++;
+        // speculative starts in the group layouts (4 lanes per slot; 16 in the tail; 8 when forced)
+        const bool spec_now = R.spec && P.camlist && (spw == 16 || spw == 8 || (XRT_SPEC_TAIL && spw == 4)) &&
+                              step_merged_group(P, spw) * spw == 64;
+        if (spec_now) T.S.spec_launches++;
+        if (spec_now && camlist_pending) {
+            camlist_pending = false;
+            HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_camlist(P, c->stream); }));
+        }
+        const hipError_t e = T.launch(XRT_K_STEP, [&] {
+            if (spec_now)
+                return launch_step_spec(P, dP, list, ci, out, co, cz, R.spec_visits, poll.live_part_max, spw, c->stream);
+            if (R.merged)
+                return launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
+                                          poll.live_hint, poll.live_part_max, c->stream);
+            return launch_step(P, dP, list, ci, out, co, cz, L.req(1), R.step_visits, blocks, poll.live_hint, R.step_tri,
+                               c->stream);
+        });
+        if (e != hipSuccess) return hip_err(c, e, "k_step");
+        const int rc = poll.after(it, co);
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
+// The wavefront loop: k_shade reads list[i & 1] and appends the surviving slots to the other
+// list (two alternating counter arrays; it twists its slots' rings in-line), k_trace traces
+// them and clears the counters k_shade read, and two-level scenes walk the BVH for the rays
+// the trace queued.
+int run_wavefront(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, LivePoll& poll,
+                  uint64_t& it) {
+    const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // one entry per thread
+    for (it = 0; it < R.cap_iters && !poll.done; ++it) {
+        const int cur = (int)(it & 1), nxt = cur ^ 1;
+        hipError_t e = T.launch(XRT_K_SHADE, [&] {
+            return launch_shade(P, L.list[cur], L.counts(cur), L.list[nxt], L.counts(nxt), L.req(1), blocks, c->stream);
+        });
+        if (e != hipSuccess) return hip_err(c, e, "k_shade");
+        e = T.launch(XRT_K_TRACE, [&] {
+            return launch_trace(P, L.list[nxt], L.counts(nxt), L.counts(cur), blocks, c->stream, false);
+        });
+        if (e != hipSuccess) return hip_err(c, e, "k_trace");
+        if (P.two_level && P.bvh_node && P.scene_kind == SCN_TRI) {
+            e = T.launch(XRT_K_DEEP, [&] { return launch_trace_deep(P, c->stream); });
+            if (e != hipSuccess) return hip_err(c, e, "k_trace_deep4");
+        }
+        const int rc = poll.after(it, L.counts(nxt));
+        if (rc) return rc;
+    }
+    return XRT_OK;
+}
+
+// the device's stats words into xrt_stats (and the counters of experiment builds to stderr)
+int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
     unsigned long long hs[48] = {0};
     HIPCHK(c, hipMemcpy(hs, P.stats, 48 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (XRT_PHASE_CLOCK)   // experiment builds: k_step_spec's visit phases (shader-clock cycles summed over waves)
@@ -1107,37 +1142,85 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
     S.pix_windows = hs[kStatsPix], S.pix_stride4 = hs[kStatsPix + 1], S.pix_frustum = hs[kStatsPix + 2];
     S.pix_frustum_overflow = hs[kStatsPix + 3], S.pix_shadow_list = hs[kStatsPix + 4];
     S.pix_shadow_overflow = hs[kStatsPix + 5], S.pix_flushes = hs[kStatsPix + 6];
-    S.schedule = pixel   ? XRT_SCHED_PIXEL
-                 : !fused ? XRT_SCHED_WAVEFRONT
-                 : bvh    ? XRT_SCHED_STEP_BVH
-                 : merged ? XRT_SCHED_STEP_MERGED
-                 : use_step_tri(P) ? XRT_SCHED_STEP_TRI : XRT_SCHED_STEP;
+    return XRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// wait: 0 = none (host output: the library owns the framebuffer), 1 = the whole device
+// (xrt_render_device), 2 = the caller's stream `wait_stream` (xrt_render_device_after)
+static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st,
+                       int wait = 0, hipStream_t wait_stream = nullptr) {
+    const auto t_start = std::chrono::steady_clock::now();
+    int rc = check_render(c, p);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (wait == 1) {
+        HIPCHK(c, hipDeviceSynchronize());
+    } else if (wait == 2) {
+        HIPCHK(c, hipEventRecord(c->wait_ev, wait_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->wait_ev, 0));
+    }
+    const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;
+    const size_t npix = (size_t)p->width * p->height;
+    if (n == 0) return render_empty_shard(c, p, d_out, h_out, st, t_start);
+
+    // buffers, parameters, plan
+    if ((rc = grow_slots(c, n)) || (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float))))) return rc;
+    float* fb = d_out ? d_out : as<float>(c->fb);   // the caller's device image, or the context's own
+    KParams P = render_params(c, p, n, fb);
+    const RenderPlan R = plan_render(P, p);
+    if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
+    P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep;
+    const size_t lcap = (size_t)P.n_part * P.part_cap;
+    const LiveLists L{{as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap}, as<uint32_t>(c->counts)};
+    P.req = as<uint32_t>(c->lists) + 2 * lcap;
+    if ((rc = setup_deep(c, P))) return rc;
+    if (R.camlist) {   // the pixels' camera-ray triangle lists: k_step_spec's candidates
+        if ((rc = ensure(c, c->camlist, n * sizeof(uint4)))) return rc;
+        P.camlist = as<uint4>(c->camlist);
+    }
+    xrt_stats S{};
+    S.path_slots = n;
+    S.samples = (uint64_t)n * p->spp;
+    LaunchTimer T{c, S, (p->flags & XRT_FLAG_TIMING) != 0, {}, {}};
+
+    // seed
+    if (!(p->flags & XRT_FLAG_ACCUMULATE))
+        HIPCHK(c, hipMemsetAsync(fb, 0, npix * 3 * sizeof(float), c->stream));
+    else if (h_out)   // the caller's Image is the accumulator (Src/renderer.cpp:75)
+        HIPCHK(c, hipMemcpyAsync(fb, h_out, npix * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(P.stats, 0, 512, c->stream));
+    if ((rc = seed_paths(c, P, R, L, T))) return rc;
+
+    // run, finish
+    LivePoll poll{c, P.n_part, R.poll_every, R.ahead, R.merged && !P.spw_req, n, P.part_cap};
+    uint64_t it = 0;
+    if (!R.pixel && (rc = R.fused ? run_fused(c, P, R, L, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it)))
+        return rc;
+    HIPCHK(c, T.launch(XRT_K_FINISH, [&] { return launch_finish(P, c->stream); }));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!R.pixel && !poll.done) {
+        // the iteration cap was reached without observing an empty list: verify
+        uint32_t left[kMaxParts] = {0};
+        HIPCHK(c, hipMemcpy(left, L.counts(R.fused ? it % 3 : it & 1), P.n_part * 4, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < P.n_part; ++k)
+            if (left[k] != 0) return set_err(c, XRT_ERR_HIP, "iteration cap reached with live paths");
+    }
+
+    // stats
+    if ((rc = read_stats(c, P, S))) return rc;
+    S.iterations = it;
+    S.schedule = (uint64_t)R.schedule;
     S.partitions = P.n_part;
-    if (fused && !pixel) S.visits_per_launch = step_visits;
-    if (merged && !pixel) {
+    if (R.fused && !R.pixel) S.visits_per_launch = R.step_visits;
+    if (R.merged && !R.pixel) {
         S.slots_per_wave = step_merged_spw(P, n);   // the layout of the first launch (every launch's: layout_launches)
         S.group_lanes = step_merged_group(P, S.slots_per_wave);
     }
-    if (timing) {
-        const bool trace = exp_env("XRT_TRACE_LAUNCHES") != nullptr;   // experiments: per-launch times
-        for (size_t q = 0; q < ev_use.size(); ++q) {
-            const auto& u = ev_use[q];
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->events[u.second], c->events[u.second + 1]) == hipSuccess)
-                S.kernel_ms[u.first] += ms;
-            if (trace) {
-                float gap = 0.0f;
-                if (q) (void)hipEventElapsedTime(&gap, c->events[ev_use[q - 1].second + 1], c->events[u.second]);
-                std::fprintf(stderr, "[xrt] launch %zu kernel %d %.3f ms (gap %.3f)%s", q, u.first, ms, gap,
-                             u.first == XRT_K_STEP && q < launch_live.size() + 2 ? "" : "\n");
-                if (u.first == XRT_K_STEP) {
-                    const size_t si = step_idx++;
-                    std::fprintf(stderr, " live %llu\n",
-                                 si < launch_live.size() ? (unsigned long long)launch_live[si] : 0ull);
-                }
-            }
-        }
-    }
+    T.read_out();
     if (h_out) HIPCHK(c, hipMemcpy(h_out, fb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     S.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (st) *st = S;
