@@ -10,6 +10,7 @@
  *   - the area lights in Scene::m_areaLights order             (Src/scene.h:44, scene.cpp:166-188),
  *   - the pinhole camera (c2w, scale, aspect)                   (Src/camera.h:10-11,37-60),
  *   - the integrator kind and its max depth                     (Src/integrator.h:198-291,76-120,401-478),
+ *   - for WhittedIntegrator the delta lights in Scene::m_deltaLights order (Src/scene.cpp:161-163),
  * and it must fill an Image of W*H float3 in place with the per-pixel sample mean
  * (Src/renderer.cpp:29-81,98; Src/image.h:46-78).  Every entry point below maps onto
  * one of those steps.  The C++ HipRenderer (include/xrt/renderer.h) is the
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define XRT_ABI_VERSION 12
+#define XRT_ABI_VERSION 13
 
 /* ---- status codes ---------------------------------------------------------------- */
 enum {
@@ -52,7 +53,12 @@ enum { XRT_OBJ_MESH = 0, XRT_OBJ_SPHERE = 1, XRT_OBJ_BOX = 2 };
  * XRT_LIGHT_SPHERE_AREA: the same light built with AREA_SAMPLING (Src/light.h:131-135,185-191:
  * a uniform point on the sphere, UniformSampleSphere Src/light.cpp:99-105, pdf 2 tmax^3/|d.n|) */
 enum { XRT_LIGHT_QUAD = 0, XRT_LIGHT_TRIANGLE = 1, XRT_LIGHT_SPHERE = 2, XRT_LIGHT_SPHERE_AREA = 3 };
-enum { XRT_MAT_NONE = 0, XRT_MAT_LAMBERT = 1 };
+/* XRT_MAT_METAL / XRT_MAT_GLASS: Object::materialType() returning MaterialType::Metals / Glass
+ * (Src/geometry.h:703), the mirror and dielectric branches of WhittedIntegrator
+ * (Src/integrator.h:344-381).  They are valid only under XRT_INTEGRATOR_WHITTED: every other
+ * integrator would call the material's own BxDF there, which the backend cannot know, and
+ * returns XRT_ERR_UNSUPPORTED for a scene that holds one. */
+enum { XRT_MAT_NONE = 0, XRT_MAT_LAMBERT = 1, XRT_MAT_METAL = 2, XRT_MAT_GLASS = 3 };
 
 /* One Object (Src/primitive.h:40-95) in Scene::m_objects iteration order. */
 typedef struct {
@@ -90,6 +96,18 @@ typedef struct {
     const xrt_light* lights;
 } xrt_scene_desc;
 
+/* One DeltaLight (Src/light.h:11-49) in Scene::m_deltaLights order (a std::vector: push-back
+ * order, Src/scene.cpp:161-163), world space.  Only WhittedIntegrator reads them. */
+enum { XRT_DLIGHT_POINT = 0, XRT_DLIGHT_DISTANT = 1 };
+typedef struct {
+    int32_t kind;       /* XRT_DLIGHT_*                                                   */
+    float pos[3];       /* PointLight::pos: multVecMatrix(Vec3f(0)) (Src/light.cpp:115-118) */
+    float dir[3];       /* DistantLight::dir: normalize(multDirMatrix((0,0,-1))) (:130-134) */
+    float color[3];     /* DeltaLight::color                                              */
+    float intensity;    /* DeltaLight::intensity                                          */
+} xrt_delta_light;
+#define XRT_MAX_DELTA_LIGHTS 8   /* most delta lights a context takes */
+
 /* The scene medium.  kind XRT_MEDIUM_HETEROGENEOUS: HeterogeneousMedium over a dense
  * density grid standing in for DensityGrid (Src/grid.h:9-15): OpenVDB
  * BoxSampler::wsSample semantics — world -> index by (p - origin) / voxel_size, voxel
@@ -125,8 +143,17 @@ enum {
     XRT_INTEGRATOR_VPT = 2,       /* VolumePathTracing(maxDepth)       Src/integrator.h:401-478 */
     XRT_INTEGRATOR_INDIRECT = 3,  /* IndirectIntegrator(maxDepth)      Src/integrator.h:122-190 */
     XRT_INTEGRATOR_NORMAL = 4,    /* NormalIntegrator (shading normal) Src/integrator.h:22-74   */
-    XRT_INTEGRATOR_VPT_NEE = 5    /* VolumePathTracingNEE(maxDepth)    Src/integrator.h:481-636 */
+    XRT_INTEGRATOR_VPT_NEE = 5,   /* VolumePathTracingNEE(maxDepth)    Src/integrator.h:481-636 */
+    XRT_INTEGRATOR_WHITTED = 6    /* WhittedIntegrator(maxDepth)       Src/integrator.h:294-398 */
 };
+/* WhittedIntegrator limits.  It runs only over scenes that fit the LDS-resident scene carve
+ * (the scenes the fused and pixel schedules serve: triangle, sphere and mixed scenes up to
+ * 64 KiB); larger (two-level) scenes return XRT_ERR_UNSUPPORTED.  A glass hit pushes two
+ * rays, so a scene with a glass object has a ray tree of up to 2^(max_depth + 1) leaves and
+ * max_depth above XRT_WHITTED_MAX_DEPTH returns XRT_ERR_UNSUPPORTED; scenes without glass are
+ * chains and take any max_depth.  The schedule flags XRT_FLAG_WAVEFRONT, NO_PIXEL, NO_MERGED,
+ * NO_SPEC, NO_GROUP and DEEP_* have no effect on it. */
+#define XRT_WHITTED_MAX_DEPTH 4
 enum {
     XRT_FLAG_TIMING = 1u,      /* time every kernel with HIP events (xrt_stats.kernel_ms)     */
     XRT_FLAG_WAVEFRONT = 2u,   /* force the multi-pass schedule (k_shade + k_trace) even when
@@ -181,7 +208,9 @@ enum {
  * timed as XRT_K_STEP) */
 enum {
     XRT_SCHED_WAVEFRONT = 0, XRT_SCHED_STEP = 1, XRT_SCHED_STEP_TRI = 2, XRT_SCHED_STEP_MERGED = 3,
-    XRT_SCHED_STEP_BVH = 4, XRT_SCHED_PIXEL = 5
+    XRT_SCHED_STEP_BVH = 4, XRT_SCHED_PIXEL = 5,
+    XRT_SCHED_WHITTED = 6   /* WhittedIntegrator: one wave per pixel, one lane per sample, the whole
+                               ray tree of a sample in its lane (k_whitted; timed as XRT_K_STEP) */
 };
 
 typedef struct {
@@ -217,6 +246,12 @@ typedef struct {
     uint64_t pix_shadow_overflow;  /* pixels whose occluder list overflowed (BVH walks)     */
     uint64_t pix_flushes;        /* deferred-shading queue flushes                          */
     uint64_t spec_launches;      /* merged schedule: step launches with speculative starts  */
+    /* WhittedIntegrator (XRT_SCHED_WHITTED); segments = Scene::intersect calls, shadow_rays =
+     * Scene::occluded calls, draws = 2 * samples there */
+    uint64_t whit_rays;          /* rays popped from the queue (depth-overflow pops included) */
+    uint64_t whit_depth_cut;     /* ... of them with depth > max_depth                       */
+    uint64_t whit_refract;       /* glass hits with kr < 1 (a refracted and a reflected ray) */
+    uint64_t whit_tir;           /* glass hits with kr >= 1 (total internal reflection)      */
 } xrt_stats;
 
 /* ---- context ----------------------------------------------------------------------- */
@@ -241,6 +276,11 @@ int  xrt_upload_scene(xrt_ctx* ctx, const xrt_scene_desc* scene);
  * PinholeCamera::scale = tan(0.5*deg2rad(FOV)) and aspect_ratio (Src/camera.h:37-47) */
 int  xrt_set_camera(xrt_ctx* ctx, const float c2w[16], float scale, float aspect);
 int  xrt_set_medium(xrt_ctx* ctx, const xrt_medium_desc* medium);
+/* The delta lights of the scene (Scene::getDeltaLights(), Src/scene.h), in order; n = 0 clears
+ * them, n > XRT_MAX_DELTA_LIGHTS returns XRT_ERR_UNSUPPORTED.  They belong to the context, not
+ * to the uploaded scene: xrt_upload_scene does not clear them.  On a multi-device context the
+ * call fans out like every other. */
+int  xrt_set_delta_lights(xrt_ctx* ctx, const xrt_delta_light* lights, uint32_t n);
 /* Sparse heterogeneous density in leaf bricks (the layout NanoVDB / OpenVDB give a grid:
  * 8^3-voxel leaves, Src/examples/nanovdb_convert.cpp, Src/grid.h:22-83).  The grid's
  * index space [0, nx) x [0, ny) x [0, nz) is cut into XRT_BRICK^3 bricks;
@@ -327,6 +367,17 @@ int xrt_hscene_add_sphere_light_area(xrt_hscene* s, const char* name, const floa
                                      const float Le[3]);
 /* Scene::addObj(name, medium->makeObject()): a BoxMesh over the medium's bounds */
 int xrt_hscene_add_medium_box(xrt_hscene* s, const char* name, const float pmin[3], const float pmax[3]);
+/* Scene::addDeltaLight(name, PointLight / DistantLight(l2w, color, intensity)): l2w is the
+ * row-major lightToWorld; pos / dir are computed as the reference constructors do */
+int xrt_hscene_add_point_light(xrt_hscene* s, const char* name, const float l2w[16], const float color[3],
+                               float intensity);
+int xrt_hscene_add_distant_light(xrt_hscene* s, const char* name, const float l2w[16], const float color[3],
+                                 float intensity);
+/* Scene::getDeltaLights() flattened, in push-back order; valid until the next mutation */
+int xrt_hscene_delta_lights(xrt_hscene* s, const xrt_delta_light** out, uint32_t* n);
+/* Re-tag the object `object_name` (added earlier) with a material whose materialType() is the
+ * one XRT_MAT_* names: Lambert keeps the object's albedo (0 if it had none), NONE drops it */
+int xrt_hscene_set_material(xrt_hscene* s, const char* object_name, int32_t material);
 /* Flatten in unordered_map iteration order.  Pointers stay valid until the next
  * mutation or destroy. */
 int xrt_hscene_flatten(xrt_hscene* s, xrt_scene_desc* out);
@@ -355,6 +406,10 @@ int xrt_test_powf(xrt_ctx* ctx, const float* x, uint32_t n, float y, float* out)
  * 1.0f / b, mode 1 its division by the constant c (rc = 1.0f / c) against x / c; returns the
  * mismatch count and up to 16 mismatching inputs (0xffffffff = unused) */
 int xrt_test_fastdiv(xrt_ctx* ctx, uint32_t mode, float c, float rc, uint64_t* n_bad, uint32_t* first_bad16);
+/* k_whitted's own reflect / refract / fresnel / normalize (Src/geometry.cpp:13-16,52-89, ior
+ * 1.3) over in[i] = {I.xyz, N.xyz}: out[i] = {reflect.xyz, refract.xyz, kr, normalize(reflect).xyz,
+ * normalize(refract).xyz} (13 floats) */
+int xrt_test_whitted_math(xrt_ctx* ctx, const float* in, uint32_t n, float* out);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,9 @@
 // xrt/integrator.h — the reference's integrators (Src/integrator.h): GIIntegrator
 // (:198-291), DirectIntegrator (:76-120), VolumePathTracing (:401-478) — the benchmark
 // configs — and IndirectIntegrator (:122-190), NormalIntegrator (:22-74),
-// VolumePathTracingNEE (:481-636).  The host objects select the GPU pass
-// schedule; they do not integrate on the CPU.  Whitted (delta lights) is not provided.
+// VolumePathTracingNEE (:481-636), WhittedIntegrator (:294-398, with the delta
+// lights of xrt/light.h).  The host objects select the GPU pass schedule; they do not
+// integrate on the CPU.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -20,7 +21,7 @@ public:
     // integrate override, Src/integrator.h:9-17).  HipRenderer renders the built-in kinds
     // on the GPU and reports XRT_ERR_UNSUPPORTED for custom ones, which only a CPU
     // renderer calling integrate() per sample can run.
-    enum class Kind { GI, Direct, VolumePathTracing, Indirect, Normal, VolumePathTracingNEE, Custom };
+    enum class Kind { GI, Direct, VolumePathTracing, Indirect, Normal, VolumePathTracingNEE, Whitted, Custom };
     Integrator() : kind_(Kind::Custom), maxDepth_(0) {}
     explicit Integrator(Kind k, uint32_t maxDepth) : kind_(k), maxDepth_(maxDepth) {}
     virtual ~Integrator() = default;
@@ -73,4 +74,9 @@ public:
 class VolumePathTracingNEE : public Integrator {
 public:
     explicit VolumePathTracingNEE(uint32_t maxDepth) : Integrator(Kind::VolumePathTracingNEE, maxDepth) {}
+};
+
+class WhittedIntegrator : public Integrator {
+public:
+    WhittedIntegrator(uint32_t maxDepth = 3) : Integrator(Kind::Whitted, maxDepth) {}
 };

@@ -2,13 +2,52 @@
 // Src/light.cpp).  Construction applies lightToWorld with multVecMatrix exactly like the
 // reference constructors (Src/light.cpp:7-14,32-39,84-91); sampling runs on the GPU.
 // makeObject() builds the same emitter objects as the reference (Src/light.cpp:35-41,70-82,93-97).
-// Delta lights (PointLight/DistantLight) are only used by WhittedIntegrator, which is out of
-// scope, and are not provided.
+// DeltaLight, PointLight, DistantLight (Src/light.h:11-49, Src/light.cpp:115-142) are the
+// lights of WhittedIntegrator: their constructors compute pos / dir on the host exactly as the
+// reference's do; sample() runs on the GPU (whitted.hip).
 #pragma once
 #include <memory>
 
 #include "geometry.h"
 #include "primitive.h"
+
+// The GPU samples the two reference kinds; Scene::flattenDeltaLights tells them apart by
+// class, and a caller's own DeltaLight subclass (its sample() cannot run on the GPU) makes
+// HipRenderer::render fail with XRT_ERR_INVALID.
+class DeltaLight {
+public:
+    DeltaLight(const Matrix44f& l2w, const Vec3f& c = 1, const float& i = 1) : color(c), intensity(i), lightToWorld(l2w) {}
+    virtual ~DeltaLight() {}
+
+    Vec3f color;
+    float intensity;
+    Matrix44f lightToWorld;
+};
+
+// the default direction is (0,0,-1) (Src/light.h:24-36, Src/light.cpp:130-134)
+class DistantLight : public DeltaLight {
+public:
+    DistantLight(const Matrix44f& l2w, const Vec3f& c = 1, const float& i = 1) : DeltaLight(l2w, c, i) {
+        l2w.multDirMatrix(Vec3f(0, 0, -1), dir);
+        dir = normalize(dir);   // in case the matrix scales the light
+    }
+    Vec3f direction() const { return dir; }
+
+private:
+    Vec3f dir;
+};
+
+// the default position is (0,0,0) (Src/light.h:38-49, Src/light.cpp:115-118)
+class PointLight : public DeltaLight {
+public:
+    PointLight(const Matrix44f& l2w, const Vec3f& c = 1, const float& i = 100.0) : DeltaLight(l2w, c, i) {
+        l2w.multVecMatrix(Vec3f(0), pos);
+    }
+    Vec3f position() const { return pos; }
+
+private:
+    Vec3f pos;
+};
 
 class AreaLight {
 public:

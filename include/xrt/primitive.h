@@ -39,6 +39,7 @@ public:
     MaterialType materialType() const;
     Kind kind() const { return m_kind; }
     const Material* material() const { return m_material; }
+    void setMaterial(Material* material) { m_material = material; }   // non-owning, as the constructor's
     const AreaLight* areaLight() const { return m_areaLight; }
     const Medium* medium() const { return m_medium; }
 

@@ -33,6 +33,15 @@ public:
     void build() {}
     void addAreaLight(std::string name, std::unique_ptr<AreaLight> light);
     const std::vector<std::unique_ptr<AreaLight>>& getAreaLights() const { return m_areaLights; }
+    // Scene::addDeltaLight / getDeltaLights (Src/scene.cpp:161-163): a vector, push-back order;
+    // the name is unused there too
+    void addDeltaLight(std::string name, std::unique_ptr<DeltaLight> light);
+    const std::vector<std::unique_ptr<DeltaLight>>& getDeltaLights() const { return m_deltaLights; }
+    // the delta lights as the C ABI takes them (xrt_set_delta_lights), in order; valid until
+    // the next addDeltaLight
+    const std::vector<xrt_delta_light>& flattenDeltaLights() const;
+    // the object added as `name`, or nullptr
+    Object* findObject(const std::string& name);
     // uniform choice among the area lights (Src/scene.cpp:182-188): one draw
     const AreaLight* sampleAreaLight(Sampler& sampler, float& pdf) const;
     // Scene::intersect / Scene::occluded (Src/scene.cpp:190-211), answered on the GPU by
@@ -68,6 +77,8 @@ public:
 
 private:
     std::vector<std::unique_ptr<AreaLight>> m_areaLights;
+    std::vector<std::unique_ptr<DeltaLight>> m_deltaLights;
+    mutable std::vector<xrt_delta_light> f_dlights;
     std::unordered_map<std::string, std::unique_ptr<Object>> m_objects;
     std::vector<std::unique_ptr<Material>> m_material;
     mutable std::string m_error;

@@ -17,27 +17,34 @@ if os.environ.get("XRT_LIB"):   # experiment builds (csrc/Makefile `variant` -> 
     _v = os.path.join(HERE, "variants", os.environ["XRT_LIB"])
     LIB_PATH = _v if os.path.exists(_v) else os.path.join(HERE, os.environ["XRT_LIB"])
 
-XRT_ABI_VERSION = 12  # include/xrt.h XRT_ABI_VERSION
+XRT_ABI_VERSION = 13  # include/xrt.h XRT_ABI_VERSION
 XRT_OK = 0
 XRT_OBJ_MESH, XRT_OBJ_SPHERE, XRT_OBJ_BOX = 0, 1, 2
 XRT_LIGHT_QUAD, XRT_LIGHT_TRIANGLE, XRT_LIGHT_SPHERE, XRT_LIGHT_SPHERE_AREA = 0, 1, 2, 3
-XRT_MAT_NONE, XRT_MAT_LAMBERT = 0, 1
+XRT_MAT_NONE, XRT_MAT_LAMBERT, XRT_MAT_METAL, XRT_MAT_GLASS = 0, 1, 2, 3
+MATERIALS = {"none": XRT_MAT_NONE, "lambert": XRT_MAT_LAMBERT, "metal": XRT_MAT_METAL, "glass": XRT_MAT_GLASS}
+XRT_DLIGHT_POINT, XRT_DLIGHT_DISTANT = 0, 1
+XRT_MAX_DELTA_LIGHTS = 8
 XRT_INTEGRATOR_GI, XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_VPT = 0, 1, 2
 XRT_INTEGRATOR_INDIRECT, XRT_INTEGRATOR_NORMAL, XRT_INTEGRATOR_VPT_NEE = 3, 4, 5
+XRT_INTEGRATOR_WHITTED = 6
+XRT_WHITTED_MAX_DEPTH = 4
+XRT_ERR_INVALID, XRT_ERR_UNSUPPORTED = -1, -5
 XRT_MEDIUM_HETEROGENEOUS, XRT_MEDIUM_HOMOGENEOUS_MIS, XRT_MEDIUM_HOMOGENEOUS_ACHROMATIC, XRT_MEDIUM_HOMOGENEOUS_NOMIS = 0, 1, 2, 3
 XRT_FLAG_TIMING, XRT_FLAG_WAVEFRONT, XRT_FLAG_NO_MERGED, XRT_FLAG_NO_GROUP, XRT_FLAG_ACCUMULATE = 1, 2, 4, 8, 16
 XRT_FLAG_DEEP_SINGLE, XRT_FLAG_DEEP_QUAD, XRT_FLAG_NO_PIXEL = 32, 64, 128
 XRT_FLAG_NO_SPEC = 256
 XRT_SCHED_WAVEFRONT, XRT_SCHED_STEP, XRT_SCHED_STEP_TRI, XRT_SCHED_STEP_MERGED, XRT_SCHED_STEP_BVH = 0, 1, 2, 3, 4
-XRT_SCHED_PIXEL = 5
-SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel")
+XRT_SCHED_PIXEL, XRT_SCHED_WHITTED = 5, 6
+SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel", "whitted")
 XRT_K_SEED, XRT_K_TRACE, XRT_K_SHADE, XRT_K_FINISH, XRT_K_STEP, XRT_K_REFILL, XRT_K_DEEP, XRT_K_COUNT = \
     0, 1, 2, 3, 4, 5, 6, 7
 LAYOUTS = (64, 32, 16, 8, 4)   # xrt_stats.layout_launches: slots per wave
 KERNEL_NAMES = ("seed", "trace", "shade", "finish", "step", "refill", "trace_deep4")
 
 INTEGRATORS = {"gi": XRT_INTEGRATOR_GI, "direct": XRT_INTEGRATOR_DIRECT, "vpt": XRT_INTEGRATOR_VPT,
-               "indirect": XRT_INTEGRATOR_INDIRECT, "normal": XRT_INTEGRATOR_NORMAL, "vpt_nee": XRT_INTEGRATOR_VPT_NEE}
+               "indirect": XRT_INTEGRATOR_INDIRECT, "normal": XRT_INTEGRATOR_NORMAL, "vpt_nee": XRT_INTEGRATOR_VPT_NEE,
+               "whitted": XRT_INTEGRATOR_WHITTED}
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -53,6 +60,11 @@ class XrtLight(C.Structure):
     _fields_ = [("kind", C.c_int32), ("v0", C.c_float * 3), ("v1", C.c_float * 3),
                 ("v2", C.c_float * 3), ("center", C.c_float * 3), ("radius", C.c_float),
                 ("Le", C.c_float * 3)]
+
+
+class XrtDeltaLight(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pos", C.c_float * 3), ("dir", C.c_float * 3), ("color", C.c_float * 3),
+                ("intensity", C.c_float)]
 
 
 class XrtSceneDesc(C.Structure):
@@ -97,7 +109,9 @@ class XrtStats(C.Structure):
                 ("rng_twists", C.c_uint64), ("layout_launches", C.c_uint64 * 5),
                 ("pix_windows", C.c_uint64), ("pix_stride4", C.c_uint64), ("pix_frustum", C.c_uint64),
                 ("pix_frustum_overflow", C.c_uint64), ("pix_shadow_list", C.c_uint64),
-                ("pix_shadow_overflow", C.c_uint64), ("pix_flushes", C.c_uint64), ("spec_launches", C.c_uint64)]
+                ("pix_shadow_overflow", C.c_uint64), ("pix_flushes", C.c_uint64), ("spec_launches", C.c_uint64),
+                ("whit_rays", C.c_uint64), ("whit_depth_cut", C.c_uint64), ("whit_refract", C.c_uint64),
+                ("whit_tir", C.c_uint64)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("kernel_ms", "launches", "layout_launches")}
@@ -127,6 +141,7 @@ SIGNATURES = {
     "xrt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(XrtSceneDesc)]),
     "xrt_set_camera": (C.c_int, [C.c_void_p, f32p, C.c_float, C.c_float]),
     "xrt_set_medium": (C.c_int, [C.c_void_p, C.POINTER(XrtMediumDesc)]),
+    "xrt_set_delta_lights": (C.c_int, [C.c_void_p, C.POINTER(XrtDeltaLight), C.c_uint32]),
     "xrt_set_medium_bricks": (C.c_int, [C.c_void_p, C.POINTER(XrtMediumDesc), C.POINTER(XrtBrickGrid)]),
     "xrt_render": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), f32p, C.POINTER(XrtStats)]),
     "xrt_render_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.POINTER(XrtStats)]),
@@ -144,6 +159,10 @@ SIGNATURES = {
     "xrt_hscene_add_sphere_light": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_float, f32p]),
     "xrt_hscene_add_sphere_light_area": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_float, f32p]),
     "xrt_hscene_add_medium_box": (C.c_int, [C.c_void_p, C.c_char_p, f32p, f32p]),
+    "xrt_hscene_add_point_light": (C.c_int, [C.c_void_p, C.c_char_p, f32p, f32p, C.c_float]),
+    "xrt_hscene_add_distant_light": (C.c_int, [C.c_void_p, C.c_char_p, f32p, f32p, C.c_float]),
+    "xrt_hscene_delta_lights": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(XrtDeltaLight)), u32p]),
+    "xrt_hscene_set_material": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "xrt_hscene_flatten": (C.c_int, [C.c_void_p, C.POINTER(XrtSceneDesc)]),
     "xrt_hscene_object_name": (C.c_char_p, [C.c_void_p, C.c_uint32]),
     "xrt_pinhole_scale": (C.c_float, [C.c_float]),
@@ -154,6 +173,7 @@ SIGNATURES = {
     "xrt_test_powf": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_float, f32p]),
     "xrt_query": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_int32, C.POINTER(XrtHit)]),
     "xrt_tonemap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint8)]),
+    "xrt_test_whitted_math": (C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
     "xrt_test_fastdiv": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_uint64), u32p]),
 }
 

@@ -18,6 +18,20 @@ public:
     FacadeMedium() : Medium(0.0f) {}
     std::unique_ptr<Object> makeObject() override { return nullptr; }
 };
+// A material that is only its type tag: WhittedIntegrator reads nothing else of a metal or
+// glass object (Src/integrator.h:344-381)
+class TagMaterial : public Material {
+public:
+    explicit TagMaterial(MaterialType t) : m_type(t) {}
+    MaterialType materialType() const override { return m_type; }
+
+private:
+    MaterialType m_type;
+};
+
+Matrix44f m44(const float* m) {
+    return Matrix44f(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11], m[12], m[13], m[14], m[15]);
+}
 }  // namespace
 
 struct xrt_hscene {
@@ -133,6 +147,50 @@ int xrt_hscene_add_medium_box(xrt_hscene* s, const char* name, const float pmin[
     if (!s || !name || !pmin || !pmax) return XRT_ERR_INVALID;
     if (s->media.empty()) s->media.push_back(std::make_unique<FacadeMedium>());
     s->scene.addObj(name, std::make_unique<BoxMesh>(AABB{v3(pmin), v3(pmax)}, s->media[0].get()));
+    return XRT_OK;
+}
+
+int xrt_hscene_add_point_light(xrt_hscene* s, const char* name, const float l2w[16], const float color[3],
+                               float intensity) {
+    if (!s || !name || !l2w || !color) return XRT_ERR_INVALID;
+    s->scene.addDeltaLight(name, std::make_unique<PointLight>(m44(l2w), v3(color), intensity));
+    return XRT_OK;
+}
+
+int xrt_hscene_add_distant_light(xrt_hscene* s, const char* name, const float l2w[16], const float color[3],
+                                 float intensity) {
+    if (!s || !name || !l2w || !color) return XRT_ERR_INVALID;
+    s->scene.addDeltaLight(name, std::make_unique<DistantLight>(m44(l2w), v3(color), intensity));
+    return XRT_OK;
+}
+
+int xrt_hscene_delta_lights(xrt_hscene* s, const xrt_delta_light** out, uint32_t* n) {
+    if (!s || !out || !n) return XRT_ERR_INVALID;
+    const std::vector<xrt_delta_light>& d = s->scene.flattenDeltaLights();
+    *out = d.data();
+    *n = (uint32_t)d.size();
+    return XRT_OK;
+}
+
+int xrt_hscene_set_material(xrt_hscene* s, const char* object_name, int32_t material) {
+    if (!s || !object_name) return XRT_ERR_INVALID;
+    Object* ob = s->scene.findObject(object_name);
+    if (!ob) {
+        s->err = std::string("no object named ") + object_name;
+        return XRT_ERR_INVALID;
+    }
+    switch (material) {
+        case XRT_MAT_NONE: ob->setMaterial(nullptr); break;
+        case XRT_MAT_LAMBERT: {
+            const auto* lam = dynamic_cast<const Lambert*>(ob->material());
+            ob->setMaterial(s->scene.ownMaterial(std::make_unique<Lambert>(lam ? lam->albedo() : Vec3f(0.0f))));
+            break;
+        }
+        case XRT_MAT_METAL: ob->setMaterial(s->scene.ownMaterial(std::make_unique<TagMaterial>(MaterialType::Metals))); break;
+        case XRT_MAT_GLASS: ob->setMaterial(s->scene.ownMaterial(std::make_unique<TagMaterial>(MaterialType::Glass))); break;
+        default: s->err = "unknown material"; return XRT_ERR_INVALID;
+    }
+    s->scene.markChanged();
     return XRT_OK;
 }
 

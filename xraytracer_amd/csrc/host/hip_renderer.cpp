@@ -35,6 +35,10 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
     if (rc != XRT_OK) return fail(rc, "Scene::flatten");
     if ((rc = xrt_upload_scene(m_ctx, &desc)) != XRT_OK) return fail(rc, "xrt_upload_scene");
 
+    const std::vector<xrt_delta_light>& dl = scene.flattenDeltaLights();
+    if ((rc = xrt_set_delta_lights(m_ctx, dl.data(), (uint32_t)dl.size())) != XRT_OK)
+        return fail(rc, "xrt_set_delta_lights");
+
     const Matrix44f& m = camera->cameraToWorld();
     float c2w[16];
     for (int r = 0; r < 4; ++r)
@@ -51,6 +55,7 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
         case Integrator::Kind::Indirect: p.integrator = XRT_INTEGRATOR_INDIRECT; break;
         case Integrator::Kind::Normal: p.integrator = XRT_INTEGRATOR_NORMAL; break;
         case Integrator::Kind::VolumePathTracingNEE: p.integrator = XRT_INTEGRATOR_VPT_NEE; break;
+        case Integrator::Kind::Whitted: p.integrator = XRT_INTEGRATOR_WHITTED; break;
         case Integrator::Kind::Custom:
             return fail(XRT_ERR_UNSUPPORTED, "custom Integrator subclasses have no GPU form");
     }

@@ -722,6 +722,37 @@ void Scene::addAreaLight(std::string name, std::unique_ptr<AreaLight> light) {
     m_areaLights.push_back(std::move(light));
 }
 
+void Scene::addDeltaLight(std::string, std::unique_ptr<DeltaLight> light) {
+    m_deltaLights.push_back(std::move(light));  // Src/scene.cpp:161-163
+}
+
+const std::vector<xrt_delta_light>& Scene::flattenDeltaLights() const {
+    f_dlights.clear();
+    for (const auto& l : m_deltaLights) {
+        xrt_delta_light d;
+        std::memset(&d, 0, sizeof(d));
+        d.kind = -1;   // neither reference kind: xrt_set_delta_lights refuses it
+        if (const auto* p = dynamic_cast<const PointLight*>(l.get())) {
+            d.kind = XRT_DLIGHT_POINT;
+            const Vec3f v = p->position();
+            d.pos[0] = v[0], d.pos[1] = v[1], d.pos[2] = v[2];
+        } else if (const auto* q = dynamic_cast<const DistantLight*>(l.get())) {
+            d.kind = XRT_DLIGHT_DISTANT;
+            const Vec3f v = q->direction();
+            d.dir[0] = v[0], d.dir[1] = v[1], d.dir[2] = v[2];
+        }
+        d.color[0] = l->color[0], d.color[1] = l->color[1], d.color[2] = l->color[2];
+        d.intensity = l->intensity;
+        f_dlights.push_back(d);
+    }
+    return f_dlights;
+}
+
+Object* Scene::findObject(const std::string& name) {
+    const auto it = m_objects.find(name);
+    return it == m_objects.end() ? nullptr : it->second.get();
+}
+
 int Scene::objectIndex(const Object* obj) const {
     int i = 0;
     for (const auto& kv : m_objects) {
@@ -784,11 +815,21 @@ int Scene::flatten(xrt_scene_desc* out) const {
         std::memset(&d, 0, sizeof(d));
         d.light = -1;
         d.medium = -1;
-        if (const auto* lam = dynamic_cast<const Lambert*>(ob->material())) {
-            d.material = XRT_MAT_LAMBERT;
-            put3(d.albedo, lam->albedo());
-        } else if (ob->material()) {
-            return XRT_ERR_UNSUPPORTED;
+        // Material::materialType() decides the tag, as Object::materialType() does for the
+        // reference's WhittedIntegrator (Src/integrator.h:326): a caller's own Material subclass
+        // reaches the mirror and glass branches through it.  Lambert needs its albedo.
+        if (ob->material()) {
+            const auto* lam = dynamic_cast<const Lambert*>(ob->material());
+            switch (ob->material()->materialType()) {
+                case MaterialType::Lambert:
+                    if (!lam) return XRT_ERR_UNSUPPORTED;
+                    d.material = XRT_MAT_LAMBERT;
+                    put3(d.albedo, lam->albedo());
+                    break;
+                case MaterialType::Metals: d.material = XRT_MAT_METAL; break;
+                case MaterialType::Glass: d.material = XRT_MAT_GLASS; break;
+                default: return XRT_ERR_UNSUPPORTED;
+            }
         }
         if (ob->areaLight()) {
             for (size_t i = 0; i < m_areaLights.size(); ++i)

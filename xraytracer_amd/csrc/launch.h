@@ -64,6 +64,14 @@ bool use_step_tri(const KParams& P);   // triangle scene: k_step_tri (cooperativ
 bool use_pixel(const KParams& P);
 size_t pix_lds_bytes(const KParams& P);
 hipError_t launch_pixel(const KParams& P, uint32_t* work, hipStream_t st);
+// WhittedIntegrator (whitted.hip): scenes that fit the LDS scene carve; one launch renders
+// every pixel of the shard, with launch_pixel's contract (after k_seed, before k_finish, the
+// pixel counter at `work`)
+bool use_whitted(const KParams& P);
+size_t whit_lds_bytes(const KParams& P);
+hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st);
+// k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
+hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned
 // counters out_count); twists the rings of slots that ran low in-line; clears zero
 // (next-next round).  req_count is unused by the step kernels (kept in the signature of

@@ -134,13 +134,21 @@ constexpr int kLargeObjTris = 256;  // two-level trace: mesh objects above this 
 constexpr int kSmallObjs = 256;
 constexpr unsigned kStepLds = 64u * 1024u;   // LDS budget of the fused schedule (k_step)
 constexpr int kStatsPix = 8;                // KParams::stats words 8..14: k_pixel path counters (xrt_stats pix_*)
-constexpr int kStatsPhase = 40;              // KParams::stats words 40..47: XRT_PHASE_CLOCK builds' phase cycles
+constexpr int kStatsWhit = 16;               // KParams::stats words 16..19: k_whitted's counters (xrt_stats whit_*)
+constexpr int kStatsPhase = 40;             // KParams::stats words 40..47: XRT_PHASE_CLOCK builds' phase cycles
 constexpr int kStatsWork = 32;               // KParams::stats word k_pixel counts the pixels taken in
 constexpr unsigned kPixLds = 160u * 1024u;   // k_pixel: scene + per-wave stream windows (gfx950: 160 KiB per workgroup)
 
 struct DLight {  // e1/e2/Ng precomputed on the host with the reference constructor's ops
     int kind;
     float v0[3], v1[3], v2[3], e1[3], e2[3], Ng[3], center[3], radius, Le[3];
+};
+
+// One delta light of WhittedIntegrator (xrt_delta_light): pos (point) or dir (distant), and
+// L = color * intensity, the product DeltaLight::sample returns, multiplied once on the host
+struct DDelta {
+    int kind;
+    float pos[3], dir[3], L[3];
 };
 
 struct DMedium {
@@ -179,6 +187,8 @@ struct KParams {
     const f4* box;      // [2 * n_box] (pmin, obj) (pmax, 0)
     const DObj* objs;
     const DLight* lights;
+    const DDelta* dlights;    // WhittedIntegrator's delta lights (xrt_set_delta_lights), n_dlights of them
+    int n_dlights;
     const DSeg* segs;
     const DObjBox* obj_box;   // per object, for the small-scene trace path (n_objs entries)
     const DObjPlane* obj_plane;   // per object, small triangle scenes (n_objs entries)

@@ -48,6 +48,10 @@ struct xrt_ctx {
     StepObjs step_objs{};   // kernel-argument object records of the merged-trace schedule
     StepObjs sstep{};       // two-level trace: the small objects' records (KParams::sstep)
     bool has_scene = false, has_camera = false, has_medium = false;
+    // WhittedIntegrator: the delta lights (kept across scene uploads), and whether the scene
+    // holds a metal / glass object (valid only under Whitted) or a glass one (depth limit)
+    DevBuf dlights;
+    bool has_mirror = false, has_glass = false;
     // slots
     size_t cap_slots = 0;
     DevBuf ray_o, ray_d, thr, rad, thr_prev, hit, hit2, hit3, sh_o, sh_d, sh_c, med, med2, nee;
@@ -253,6 +257,7 @@ void xrt_destroy(xrt_ctx* c) {
     free_buf(c->stri), free_buf(c->sbox), free_buf(c->splane), free_buf(c->bvh4), free_buf(c->deep);
     free_buf(c->stage), free_buf(c->q_rays), free_buf(c->q_tmax), free_buf(c->q_out);
     free_buf(c->brick_table), free_buf(c->brick_data), free_buf(c->corners), free_buf(c->camlist);
+    free_buf(c->dlights);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->poll_ev)
         if (e) (void)hipEventDestroy(e);
@@ -286,8 +291,11 @@ static int upload_scene_one(xrt_ctx* c, const xrt_scene_desc* s) {
     auto F4 = [](const Vec3f& v, float w) { return f4{v[0], v[1], v[2], w}; };
     auto bits = [](int x) { float f; std::memcpy(&f, &x, 4); return f; };
     double emax = 0.0;   // largest |e1| |e2| of a triangle (bounds |det| of every ray test)
+    bool has_mirror = false, has_glass = false;   // the context's flags change only when the upload succeeds
     for (uint32_t k = 0; k < s->n_objects; ++k) {
         const xrt_object& o = s->objects[k];
+        has_mirror = has_mirror || o.material == XRT_MAT_METAL || o.material == XRT_MAT_GLASS;
+        has_glass = has_glass || o.material == XRT_MAT_GLASS;
         if (o.light >= (int)s->n_lights || o.count < 0 || o.first < 0)
             return set_err(c, XRT_ERR_INVALID, "object " + std::to_string(k) + ": bad light index or range");
         DObj d{};
@@ -613,6 +621,7 @@ static int upload_scene_one(xrt_ctx* c, const xrt_scene_desc* s) {
         P.n_snode = (int)T.size();
     }
     c->obj_tri_first = std::move(tri_first);
+    c->has_mirror = has_mirror, c->has_glass = has_glass;
     c->has_scene = true;
     return XRT_OK;
 }
@@ -623,6 +632,30 @@ static int set_camera_one(xrt_ctx* c, const float c2w[16], float scale, float as
     c->base.scale = scale;
     c->base.aspect = aspect;
     c->has_camera = true;
+    return XRT_OK;
+}
+
+// DeltaLight::sample returns color * intensity (Src/light.cpp:127,141): multiplied once here,
+// the same float product
+static int set_delta_lights_one(xrt_ctx* c, const xrt_delta_light* lights, uint32_t n) {
+    if (!c || (n && !lights)) return XRT_ERR_INVALID;
+    if (n > XRT_MAX_DELTA_LIGHTS)
+        return set_err(c, XRT_ERR_UNSUPPORTED, "more than " + std::to_string(XRT_MAX_DELTA_LIGHTS) + " delta lights");
+    std::vector<DDelta> d(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (lights[i].kind != XRT_DLIGHT_POINT && lights[i].kind != XRT_DLIGHT_DISTANT)
+            return set_err(c, XRT_ERR_INVALID, "delta light " + std::to_string(i) + ": unknown kind");
+        d[i].kind = lights[i].kind;
+        for (int q = 0; q < 3; ++q) {
+            d[i].pos[q] = lights[i].pos[q], d[i].dir[q] = lights[i].dir[q];
+            d[i].L[q] = lights[i].color[q] * lights[i].intensity;
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = upload(c, c->dlights, d.data(), n * sizeof(DDelta));
+    if (rc) return rc;
+    c->base.dlights = as<DDelta>(c->dlights);
+    c->base.n_dlights = (int)n;
     return XRT_OK;
 }
 
@@ -758,8 +791,14 @@ int check_render(xrt_ctx* c, const xrt_render_params* p) {
     if (!c->has_scene || !c->has_camera) return set_err(c, XRT_ERR_STATE, "upload a scene and set a camera first");
     if (p->width == 0 || p->height == 0 || p->shard_count == 0 || p->shard_index >= p->shard_count)
         return set_err(c, XRT_ERR_INVALID, "bad image size or shard");
-    if (p->integrator < XRT_INTEGRATOR_GI || p->integrator > XRT_INTEGRATOR_VPT_NEE)
+    if (p->integrator < XRT_INTEGRATOR_GI || p->integrator > XRT_INTEGRATOR_WHITTED)
         return set_err(c, XRT_ERR_INVALID, "unknown integrator");
+    if (p->integrator != XRT_INTEGRATOR_WHITTED && c->has_mirror)
+        return set_err(c, XRT_ERR_UNSUPPORTED,
+                       "the scene holds a metal or glass object: only WhittedIntegrator knows those materials");
+    if (p->integrator == XRT_INTEGRATOR_WHITTED && c->has_glass && p->max_depth > XRT_WHITTED_MAX_DEPTH)
+        return set_err(c, XRT_ERR_UNSUPPORTED, "WhittedIntegrator over a scene with glass: max_depth above " +
+                                                   std::to_string(XRT_WHITTED_MAX_DEPTH) + " (XRT_WHITTED_MAX_DEPTH)");
     const bool volumetric = p->integrator == XRT_INTEGRATOR_VPT || p->integrator == XRT_INTEGRATOR_VPT_NEE;
     if (volumetric && !c->has_medium)
         return set_err(c, XRT_ERR_STATE, "VolumePathTracing needs xrt_set_medium first");
@@ -857,8 +896,9 @@ struct RenderPlan {
     // loop (fused and merged are then only what sized the partitions).  Otherwise fused: the
     // k_step loop (else k_shade + k_trace); merged: its k_step_merged form; two_level: that
     // kernel with the wave's own BVH walk; step_tri: k_step_tri in place of k_step; spec:
-    // k_step_spec in the merged schedule's group layouts, which needs the camera lists
-    bool pixel, fused, merged, two_level, step_tri, spec, camlist;
+    // k_step_spec in the merged schedule's group layouts, which needs the camera lists.
+    // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it
+    bool pixel, fused, merged, two_level, step_tri, spec, camlist, whitted;
     uint32_t n_part, part_cap;                     // live-list partitions
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
@@ -883,7 +923,12 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p) {
     R.step_tri = R.fused && !R.merged && use_step_tri(P);
     R.spec = R.merged && !R.two_level && !(p->flags & XRT_FLAG_NO_SPEC) && use_step_spec(P);
     R.camlist = R.spec && !exp_env("XRT_NO_CAMLIST");
-    R.schedule = R.pixel       ? XRT_SCHED_PIXEL
+    // WhittedIntegrator has one schedule, whatever the flags say (render_impl has refused the
+    // scenes k_whitted cannot hold): one wave per pixel, one lane per sample (whitted.hip)
+    R.whitted = p->integrator == XRT_INTEGRATOR_WHITTED;
+    if (R.whitted) R.pixel = true, R.two_level = R.merged = R.step_tri = R.spec = R.camlist = false;
+    R.schedule = R.whitted     ? XRT_SCHED_WHITTED
+                 : R.pixel     ? XRT_SCHED_PIXEL
                  : !R.fused    ? XRT_SCHED_WAVEFRONT
                  : R.two_level ? XRT_SCHED_STEP_BVH
                  : R.merged    ? XRT_SCHED_STEP_MERGED
@@ -1045,8 +1090,10 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
         // every pixel of the shard in one persistent launch; the pixel counter is a stats word
         // (zeroed with them)
         uint32_t* work = reinterpret_cast<uint32_t*>(P.stats + kStatsWork);
-        const hipError_t e = T.launch(XRT_K_STEP, [&] { return launch_pixel(P, work, c->stream); });
-        if (e != hipSuccess) return hip_err(c, e, "k_pixel");
+        const hipError_t e = T.launch(XRT_K_STEP, [&] {
+            return R.whitted ? launch_whitted(P, work, c->stream) : launch_pixel(P, work, c->stream);
+        });
+        if (e != hipSuccess) return hip_err(c, e, R.whitted ? "k_whitted" : "k_pixel");
     } else {
         HIPCHK(c, T.launch(XRT_K_REFILL, [&] {
             return R.merged ? launch_refill_merged(P, L.req(0), L.req(1), c->stream)
@@ -1142,6 +1189,8 @@ int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
     S.pix_windows = hs[kStatsPix], S.pix_stride4 = hs[kStatsPix + 1], S.pix_frustum = hs[kStatsPix + 2];
     S.pix_frustum_overflow = hs[kStatsPix + 3], S.pix_shadow_list = hs[kStatsPix + 4];
     S.pix_shadow_overflow = hs[kStatsPix + 5], S.pix_flushes = hs[kStatsPix + 6];
+    S.whit_rays = hs[kStatsWhit], S.whit_depth_cut = hs[kStatsWhit + 1], S.whit_refract = hs[kStatsWhit + 2];
+    S.whit_tir = hs[kStatsWhit + 3];
     return XRT_OK;
 }
 
@@ -1171,6 +1220,9 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
     if ((rc = grow_slots(c, n)) || (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float))))) return rc;
     float* fb = d_out ? d_out : as<float>(c->fb);   // the caller's device image, or the context's own
     KParams P = render_params(c, p, n, fb);
+    if (p->integrator == XRT_INTEGRATOR_WHITTED && !use_whitted(P))
+        return set_err(c, XRT_ERR_UNSUPPORTED,
+                       "WhittedIntegrator needs a scene that fits the LDS-resident scene carve (not a two-level scene)");
     const RenderPlan R = plan_render(P, p);
     if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
     P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep;
@@ -1289,6 +1341,15 @@ int xrt_set_camera(xrt_ctx* c, const float c2w[16], float scale, float aspect) {
     return XRT_OK;
 }
 
+int xrt_set_delta_lights(xrt_ctx* c, const xrt_delta_light* lights, uint32_t n) {
+    if (!c || c->subs.empty()) return set_delta_lights_one(c, lights, n);
+    for (xrt_ctx* d : c->subs) {
+        const int rc = set_delta_lights_one(d, lights, n);
+        if (rc) return multi_fail(c, d, rc, "xrt_set_delta_lights");
+    }
+    return XRT_OK;
+}
+
 int xrt_set_medium(xrt_ctx* c, const xrt_medium_desc* md) {
     if (!c || c->subs.empty()) return set_medium_one(c, md);
     for (xrt_ctx* d : c->subs) {
@@ -1373,6 +1434,8 @@ static int render_multi(xrt_ctx* m, const xrt_render_params* p, float* d_out, fl
             T.pix_frustum_overflow += S[i].pix_frustum_overflow, T.pix_shadow_list += S[i].pix_shadow_list;
             T.pix_shadow_overflow += S[i].pix_shadow_overflow, T.pix_flushes += S[i].pix_flushes;
             T.spec_launches += S[i].spec_launches;
+            T.whit_rays += S[i].whit_rays, T.whit_depth_cut += S[i].whit_depth_cut;
+            T.whit_refract += S[i].whit_refract, T.whit_tir += S[i].whit_tir;
             for (int k = 0; k < 5; ++k) T.layout_launches[k] += S[i].layout_launches[k];
             T.path_slots += S[i].path_slots;
             T.iterations = std::max(T.iterations, S[i].iterations);
@@ -1457,6 +1520,24 @@ int xrt_test_rng(xrt_ctx* c, const uint32_t* seeds, uint32_t n_seeds, uint32_t s
     if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n_seeds * n * 4, hipMemcpyDeviceToHost);
     free_buf(ds), free_buf(dout), free_buf(rings);
     return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_rng");
+}
+
+int xrt_test_whitted_math(xrt_ctx* c, const float* in, uint32_t n, float* out) {
+    if (c && !c->subs.empty()) c = c->subs[0];   // multi-GPU context: its first device
+    if (!c || !in || !out) return XRT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf din, dout;
+    int rc;
+    if ((rc = ensure(c, din, (size_t)n * 24 + 16)) || (rc = ensure(c, dout, (size_t)n * 52 + 16))) {
+        free_buf(din), free_buf(dout);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(din.p, in, (size_t)n * 24, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = launch_test_whitted(as<float>(din), n, as<float>(dout), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n * 52, hipMemcpyDeviceToHost);
+    free_buf(din), free_buf(dout);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_whitted_math");
 }
 
 int xrt_test_trig(xrt_ctx* c, const float* x, uint32_t n, float* out) {

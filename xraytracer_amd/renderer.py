@@ -52,6 +52,8 @@ class HipRenderer:
         cam = scene.camera
         self._check(self._lib.xrt_set_camera(self.ctx, abi.fptr(cam.c2w), C.c_float(cam.scale),
                                              C.c_float(cam.aspect)), "xrt_set_camera")
+        dl, ndl = scene.delta_lights()   # always sent: a scene without any clears the context's
+        self._check(self._lib.xrt_set_delta_lights(self.ctx, dl, ndl), "xrt_set_delta_lights")
         if scene.medium is not None:
             md = scene.medium.desc()
             if getattr(scene.medium, "sparse", False):

@@ -185,6 +185,31 @@ class SceneBundle:
         self._check(fn(self.h, name.encode(), abi.fptr(abi.f3(center)), C.c_float(radius), abi.fptr(abi.f3(Le))),
                     f"SphereLight({name})")
 
+    def add_point_light(self, name, l2w, color, intensity=100.0):
+        """PointLight(l2w, color, intensity) (Src/light.h:42-49): l2w row-major lightToWorld"""
+        m = np.ascontiguousarray(np.asarray(l2w, dtype=np.float32).reshape(16))
+        self._check(self._lib.xrt_hscene_add_point_light(self.h, name.encode(), abi.fptr(m), abi.fptr(abi.f3(color)),
+                                                         C.c_float(intensity)), f"PointLight({name})")
+
+    def add_distant_light(self, name, l2w, color, intensity=1.0):
+        """DistantLight(l2w, color, intensity) (Src/light.h:28-36)"""
+        m = np.ascontiguousarray(np.asarray(l2w, dtype=np.float32).reshape(16))
+        self._check(self._lib.xrt_hscene_add_distant_light(self.h, name.encode(), abi.fptr(m), abi.fptr(abi.f3(color)),
+                                                           C.c_float(intensity)), f"DistantLight({name})")
+
+    def set_material(self, name, material):
+        """Re-tag object `name`: "lambert" | "metal" | "glass" | "none" (call flatten() after)"""
+        self._check(self._lib.xrt_hscene_set_material(self.h, name.encode(), abi.MATERIALS[material]),
+                    f"set_material({name}, {material})")
+
+    def delta_lights(self):
+        """Scene::getDeltaLights() flattened: (pointer to XrtDeltaLight array or None, count); the
+        array lives in the host scene until its next mutation"""
+        p = C.POINTER(abi.XrtDeltaLight)()
+        n = C.c_uint32(0)
+        self._check(self._lib.xrt_hscene_delta_lights(self.h, C.byref(p), C.byref(n)), "delta_lights")
+        return (p if n.value else None), int(n.value)
+
     def add_medium(self, name, medium: Medium):
         lo, hi = medium.bounds()
         self.medium = medium
@@ -302,6 +327,46 @@ def smoke(width, height, n=128) -> SceneBundle:
     s.flatten()
     s.camera = pinhole((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, c, c, c + 2.2 * n, 1), 45.0, width, height)
     s.integrator, s.max_depth = "vpt", 10
+    return s
+
+
+# an axis-aligned cube as 12 triangles (outward winding), min corner lo, max corner hi
+def cube_triangles(lo, hi):
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    quads = [((x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)),   # +z
+             ((x1, y0, z0), (x0, y0, z0), (x0, y1, z0), (x1, y1, z0)),   # -z
+             ((x1, y0, z1), (x1, y0, z0), (x1, y1, z0), (x1, y1, z1)),   # +x
+             ((x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0)),   # -x
+             ((x0, y1, z1), (x1, y1, z1), (x1, y1, z0), (x0, y1, z0)),   # +y
+             ((x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1))]   # -y
+    tris = []
+    for a, b, c, d in quads:
+        tris += [(a, b, c), (a, c, d)]
+    return np.asarray(tris, dtype=np.float32)
+
+
+EXAMPLE_DISTANT_L2W = (0.95292, 0.289503, 0.0901785, 0, -0.0960954, 0.5704, -0.815727, 0,
+                       -0.287593, 0.768656, 0.571365, 0, 0, 0, 0, 1)            # example.cpp:59-62
+EXAMPLE_POINT_L2W = (1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0, 5.0, 5.0, -1.0, 1.0)   # example.cpp:65-69
+# What Scene::loadObj makes of the example's cube.obj: the file's `o cube` has all six faces
+# commented out, so its one object is `o plane` — the 30 x 30 quad at y = -2.2 (`f -4 -3 -2 -1`,
+# material `diffuse`, Kd 1) — split along v1-v3 as tinyobjloader splits a quad with equal diagonals
+EXAMPLE_PLANE = (((15.0, -2.2, 15.0), (15.0, -2.2, -15.0), (-15.0, -2.2, 15.0)),
+                 ((15.0, -2.2, -15.0), (-15.0, -2.2, -15.0), (-15.0, -2.2, 15.0)))
+
+
+def example(width, height) -> SceneBundle:
+    """Src/examples/example.cpp:19-70 under WhittedIntegrator(3): the geometry loadObj gets from
+    cube.obj (EXAMPLE_PLANE, Lambert Kd 1), the unit sphere at the origin (Lambert 0.58), a
+    DistantLight and a PointLight with the example's matrices, camera at (0, 0, 8), FOV 60."""
+    s = SceneBundle()
+    s.add_mesh("plane", EXAMPLE_PLANE, (1.0, 1.0, 1.0))
+    s.add_sphere("sphere_diffuse", (0.0, 0.0, 0.0), 1.0, (0.58, 0.58, 0.58))
+    s.add_distant_light("DistantLight", EXAMPLE_DISTANT_L2W, (1.0, 1.0, 1.0), 1.0)
+    s.add_point_light("PointLight", EXAMPLE_POINT_L2W, (0.63, 0.33, 0.03), 50.0)
+    s.flatten()
+    s.camera = pinhole((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 8, 1), 60.0, width, height)
+    s.integrator, s.max_depth = "whitted", 3
     return s
 
 
