@@ -146,9 +146,12 @@ enum {
     XRT_INTEGRATOR_VPT_NEE = 5,   /* VolumePathTracingNEE(maxDepth)    Src/integrator.h:481-636 */
     XRT_INTEGRATOR_WHITTED = 6    /* WhittedIntegrator(maxDepth)       Src/integrator.h:294-398 */
 };
-/* WhittedIntegrator limits.  It runs only over scenes that fit the LDS-resident scene carve
- * (the scenes the fused and pixel schedules serve: triangle, sphere and mixed scenes up to
- * 64 KiB); larger (two-level) scenes return XRT_ERR_UNSUPPORTED.  A glass hit pushes two
+/* WhittedIntegrator limits.  By default it runs only over scenes that fit the LDS-resident
+ * scene carve (the scenes the fused and pixel schedules serve: triangle, sphere and mixed
+ * scenes up to 64 KiB); larger (two-level) scenes return XRT_ERR_UNSUPPORTED.  With
+ * XRT_FLAG_WHITTED_BVH a triangle scene beyond LDS renders through its triangle BVH
+ * (XRT_SCHED_WHITTED_BVH); large sphere-only and mixed scenes, which have no triangle BVH,
+ * still return XRT_ERR_UNSUPPORTED.  A glass hit pushes two
  * rays, so a scene with a glass object has a ray tree of up to 2^(max_depth + 1) leaves and
  * max_depth above XRT_WHITTED_MAX_DEPTH returns XRT_ERR_UNSUPPORTED; scenes without glass are
  * chains and take any max_depth.  The schedule flags XRT_FLAG_WAVEFRONT, NO_PIXEL, NO_MERGED,
@@ -171,6 +174,10 @@ enum {
                                    16-slot launches start every sample beside its predecessor's
                                    last trace (k_step_spec, the default); this flag keeps them on
                                    k_step_merged — same results                                */
+    XRT_FLAG_WHITTED_BVH = 512u, /* Whitted may fall back to the global-memory BVH schedule when
+                                   the scene does not fit LDS (k_whitted_bvh: triangle scenes
+                                   with one big mesh or many, XRT_SCHED_WHITTED_BVH); a scene
+                                   that fits LDS renders exactly as without the flag           */
     XRT_FLAG_ACCUMULATE = 16u  /* Renderer::render's in-place contract (Src/renderer.cpp:75,98):
                                   each owned pixel starts from the value already in the output
                                   buffer (Image::addPixel adds to it in sample order), then
@@ -209,8 +216,10 @@ enum {
 enum {
     XRT_SCHED_WAVEFRONT = 0, XRT_SCHED_STEP = 1, XRT_SCHED_STEP_TRI = 2, XRT_SCHED_STEP_MERGED = 3,
     XRT_SCHED_STEP_BVH = 4, XRT_SCHED_PIXEL = 5,
-    XRT_SCHED_WHITTED = 6   /* WhittedIntegrator: one wave per pixel, one lane per sample, the whole
+    XRT_SCHED_WHITTED = 6,  /* WhittedIntegrator: one wave per pixel, one lane per sample, the whole
                                ray tree of a sample in its lane (k_whitted; timed as XRT_K_STEP) */
+    XRT_SCHED_WHITTED_BVH = 7   /* the same loop over a triangle scene beyond LDS, its traces through
+                                   the triangle BVH (k_whitted_bvh, XRT_FLAG_WHITTED_BVH)           */
 };
 
 typedef struct {

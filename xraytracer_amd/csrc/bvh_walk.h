@@ -1,0 +1,96 @@
+// bvh_walk.h — the per-lane walk of the triangle BVH (bvh.h), shared by the wavefront trace
+// (wavefront.hip k_trace_bvh) and the Whitted kernel for scenes beyond LDS (whitted.hip
+// k_whitted_bvh), and the small objects' plane cull of the two-level traces.
+//
+// Large triangle scenes (C4): closest hit and any-hit through the host-built BVH (bvh.h).
+// Exactness: every node box is padded beyond the float error of a Moller-Trumbore hit, a
+// child is entered when its box overlaps [0, best t] (inclusive: a later triangle at the
+// same t with a lower index must still be found), and the closest hit is the
+// lexicographic minimum of (t, original index) — the reference's in-order strict
+// `t < best` scan over all triangles (Src/scene.cpp:190-200, primitive.cpp:83-131).
+// Shadow rays test occluder triangles only and stop at the first hit (Scene::occluded).
+// One ray per lane; the traversal stack lives in LDS (P.bvh_stack entries per thread,
+// STRIDE entries apart: the block's threads interleave their stacks).
+#pragma once
+#include "bvh.h"
+#include "path_common.h"
+
+namespace xrt {
+
+template <bool ANY>
+__device__ __forceinline__ bool bvh_leaf(const KParams& P, int first, int count, v3 o, v3 d, float tmax, float& bt,
+                                         float& bu, float& bv, int& bk) {
+    for (int i = first; i < first + count; ++i) {
+        const f4 A = P.bvh_tri[3 * i], B = P.bvh_tri[3 * i + 1], C = P.bvh_tri[3 * i + 2];
+        if (ANY && B.w == 0.0f) continue;   // area-light objects never occlude
+        float t, u, v;
+        if (!ray_tri(o, d, xyz(A), xyz(B), xyz(C), t, u, v)) continue;
+        if (ANY) {
+            if (t < tmax) return true;
+        } else {
+            const int k = __float_as_int(C.w);
+            if (t < bt || (t == bt && k < bk)) bt = t, bu = u, bv = v, bk = k;
+        }
+    }
+    return false;
+}
+
+// ANY: returns occluded; else fills (bt, bu, bv, bk) (bk = -1: miss).  Closest-hit rays
+// descend into the nearer child first (entry distance) and stack the farther one, so the
+// best t shrinks early and culls more of the tree; the result does not depend on the
+// order (lexicographic (t, index) minimum over every triangle whose box overlaps).
+// top: the first ntop nodes (the breadth-first top of the tree, host/bvh.cpp) in LDS.
+// A caller that starts from a hit it already has (bt, bu, bv, bk of the small objects of a
+// two-level scene) gets the merge of both: the same (t, index) order decides.
+template <bool ANY, typename SE, int STRIDE = kBlock>
+__device__ bool bvh_trace(const KParams& P, const f4* top, int ntop, SE* stk, v3 o, v3 d, float tmax, float& bt,
+                          float& bu, float& bv, int& bk) {
+    const v3 inv = rcp3(d);
+    int sp = 0;
+    int node = 0;
+    while (true) {
+        f4 n0, n1, n2, n3;
+        if (node < ntop) {
+            const f4* N = top + 4 * node;
+            n0 = N[0], n1 = N[1], n2 = N[2], n3 = N[3];
+        } else {
+            const f4* N = P.bvh_node + 4 * (size_t)node;
+            n0 = N[0], n1 = N[1], n2 = N[2], n3 = N[3];
+        }
+        const float lim = ANY ? tmax : bt;
+        const int lcount = __float_as_int(n1.w), rcount = __float_as_int(n3.w);
+        const float el = lcount >= 0 ? bvh_enter(n0, n1, o, inv, lim) : __builtin_inff();
+        const float er = rcount >= 0 ? bvh_enter(n2, n3, o, inv, lim) : __builtin_inff();
+        const bool hl = el != __builtin_inff(), hr = er != __builtin_inff();
+        // leaves first (either order gives the same result)
+        if (hl && lcount > 0 && bvh_leaf<ANY>(P, __float_as_int(n0.w), lcount, o, d, tmax, bt, bu, bv, bk)) return true;
+        if (hr && rcount > 0 && bvh_leaf<ANY>(P, __float_as_int(n2.w), rcount, o, d, tmax, bt, bu, bv, bk)) return true;
+        const bool il = hl && lcount == 0, ir = hr && rcount == 0;
+        int next = -1;
+        if (il && ir) {
+            const bool lfirst = ANY || el <= er;
+            next = __float_as_int(lfirst ? n0.w : n2.w);
+            stk[(sp++) * STRIDE] = (SE)__float_as_int(lfirst ? n2.w : n0.w);
+        } else if (il) {
+            next = __float_as_int(n0.w);
+        } else if (ir) {
+            next = __float_as_int(n2.w);
+        }
+        if (next >= 0) {
+            node = next;
+        } else {
+            if (sp == 0) break;
+            node = (int)stk[(--sp) * STRIDE];
+        }
+    }
+    return false;
+}
+
+// Two-level scenes: the small objects' plane cull (DObjPlane, wavefront.h; step_tri.hip plane_away)
+__device__ __forceinline__ bool plane_away_w(v3 o, v3 d, const DObjPlane& pl) {
+    const float oa = pl.axis == 0 ? o.x : (pl.axis == 1 ? o.y : o.z);
+    const float da = pl.axis == 0 ? d.x : (pl.axis == 1 ? d.y : d.z);
+    return pl.axis >= 0 && (oa - pl.c) * da >= 0.0f;
+}
+
+}  // namespace xrt

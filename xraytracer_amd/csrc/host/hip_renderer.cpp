@@ -113,5 +113,7 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
     p.shard_index = 0;
     p.shard_count = 1;
     p.flags = XRT_FLAG_ACCUMULATE;   // samples are added to the Image in place (Src/renderer.cpp:75, 98)
+    // the reference's Whitted loop runs over any Scene: take the BVH schedule when LDS is too small
+    if (p.integrator == XRT_INTEGRATOR_WHITTED) p.flags |= XRT_FLAG_WHITTED_BVH;
     if ((rc = xrt_render(m_ctx, &p, image.data(), &m_stats)) != XRT_OK) return fail(rc, "xrt_render");
 }

@@ -70,6 +70,12 @@ hipError_t launch_pixel(const KParams& P, uint32_t* work, hipStream_t st);
 bool use_whitted(const KParams& P);
 size_t whit_lds_bytes(const KParams& P);
 hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st);
+// ... and triangle scenes beyond it that have the triangle BVH (one- and two-level scenes):
+// k_whitted_bvh, the same loop tracing through the BVH and the small objects' LDS copy
+// (XRT_FLAG_WHITTED_BVH; same contract)
+bool use_whitted_bvh(const KParams& P);
+size_t whit_bvh_lds_bytes(const KParams& P);
+hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st);
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bvh.h"
+#include "bvh_walk.h"
 #include "lscene.h"
 #include "path_common.h"
 
@@ -217,72 +218,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
 // Shadow rays test occluder triangles only and stop at the first hit (Scene::occluded).
 // One ray per lane; the traversal stack lives in LDS (kBvhStack entries per thread).
 
-template <bool ANY>
-__device__ __forceinline__ bool bvh_leaf(const KParams& P, int first, int count, v3 o, v3 d, float tmax, float& bt,
-                                         float& bu, float& bv, int& bk) {
-    for (int i = first; i < first + count; ++i) {
-        const f4 A = P.bvh_tri[3 * i], B = P.bvh_tri[3 * i + 1], C = P.bvh_tri[3 * i + 2];
-        if (ANY && B.w == 0.0f) continue;   // area-light objects never occlude
-        float t, u, v;
-        if (!ray_tri(o, d, xyz(A), xyz(B), xyz(C), t, u, v)) continue;
-        if (ANY) {
-            if (t < tmax) return true;
-        } else {
-            const int k = __float_as_int(C.w);
-            if (t < bt || (t == bt && k < bk)) bt = t, bu = u, bv = v, bk = k;
-        }
-    }
-    return false;
-}
-
-// ANY: returns occluded; else fills (bt, bu, bv, bk) (bk = -1: miss).  Closest-hit rays
-// descend into the nearer child first (entry distance) and stack the farther one, so the
-// best t shrinks early and culls more of the tree; the result does not depend on the
-// order (lexicographic (t, index) minimum over every triangle whose box overlaps).
-// top: the first ntop nodes (the breadth-first top of the tree, host/bvh.cpp) in LDS.
-template <bool ANY, typename SE>
-__device__ bool bvh_trace(const KParams& P, const f4* top, int ntop, SE* stk, v3 o, v3 d, float tmax, float& bt,
-                          float& bu, float& bv, int& bk) {
-    const v3 inv = rcp3(d);
-    int sp = 0;
-    int node = 0;
-    while (true) {
-        f4 n0, n1, n2, n3;
-        if (node < ntop) {
-            const f4* N = top + 4 * node;
-            n0 = N[0], n1 = N[1], n2 = N[2], n3 = N[3];
-        } else {
-            const f4* N = P.bvh_node + 4 * (size_t)node;
-            n0 = N[0], n1 = N[1], n2 = N[2], n3 = N[3];
-        }
-        const float lim = ANY ? tmax : bt;
-        const int lcount = __float_as_int(n1.w), rcount = __float_as_int(n3.w);
-        const float el = lcount >= 0 ? bvh_enter(n0, n1, o, inv, lim) : __builtin_inff();
-        const float er = rcount >= 0 ? bvh_enter(n2, n3, o, inv, lim) : __builtin_inff();
-        const bool hl = el != __builtin_inff(), hr = er != __builtin_inff();
-        // leaves first (either order gives the same result)
-        if (hl && lcount > 0 && bvh_leaf<ANY>(P, __float_as_int(n0.w), lcount, o, d, tmax, bt, bu, bv, bk)) return true;
-        if (hr && rcount > 0 && bvh_leaf<ANY>(P, __float_as_int(n2.w), rcount, o, d, tmax, bt, bu, bv, bk)) return true;
-        const bool il = hl && lcount == 0, ir = hr && rcount == 0;
-        int next = -1;
-        if (il && ir) {
-            const bool lfirst = ANY || el <= er;
-            next = __float_as_int(lfirst ? n0.w : n2.w);
-            stk[(sp++) * kBlock] = (SE)__float_as_int(lfirst ? n2.w : n0.w);
-        } else if (il) {
-            next = __float_as_int(n0.w);
-        } else if (ir) {
-            next = __float_as_int(n2.w);
-        }
-        if (next >= 0) {
-            node = next;
-        } else {
-            if (sp == 0) break;
-            node = (int)stk[(--sp) * kBlock];
-        }
-    }
-    return false;
-}
+// bvh_leaf / bvh_trace: the per-lane walk, bvh_walk.h
 
 template <int NL, typename SE>
 __global__ __launch_bounds__(kBlock) void k_trace_bvh(KParams P, const uint32_t* __restrict__ list,
@@ -337,12 +273,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_bvh(KParams P, const uint32_t*
 // [0, best t] (any-hit: [0, tmax], if not yet occluded) overlaps the BVH root; phase B
 // (k_trace_deep) walks the BVH for the queued rays alone — full waves of deep rays — and
 // merges with the same (t, index) order (bvh_leaf).  The result is the one-level trace's.
-__device__ __forceinline__ bool plane_away_w(v3 o, v3 d, const DObjPlane& pl) {   // step_tri.hip plane_away
-    const float oa = pl.axis == 0 ? o.x : (pl.axis == 1 ? o.y : o.z);
-    const float da = pl.axis == 0 ? d.x : (pl.axis == 1 ? d.y : d.z);
-    return pl.axis >= 0 && (oa - pl.c) * da >= 0.0f;
-}
-
 template <int NL>
 __global__ __launch_bounds__(kBlock) void k_trace_2a(KParams P, const uint32_t* __restrict__ list,
                                                      const uint32_t* __restrict__ count, uint32_t* zero_count) {

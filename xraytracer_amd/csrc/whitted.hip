@@ -29,8 +29,13 @@
 // Src/geometry.h:212-217).  The traces (lscene.h closest_l / occluded_l) take the direction
 // as given: a metal child's direction is not normalised, and a NaN direction (normalize of
 // refract's zero vector) misses everything, as every `t < best` test fails.
+//
+// Two kernels run this: k_whitted over a scene resident in LDS, k_whitted_bvh over a triangle
+// scene beyond LDS through its BVH (XRT_FLAG_WHITTED_BVH).  They differ in the trace policy
+// whit_integrate is instantiated with and in nothing else.
 #include <hip/hip_runtime.h>
 
+#include "bvh_walk.h"
 #include "lds_stream.h"
 #include "lscene.h"
 #include "path_common.h"
@@ -90,9 +95,25 @@ struct WhitCount {
     uint32_t seg = 0, shadow = 0, rays = 0, cut = 0, refr = 0, tir = 0;
 };
 
-// WhittedIntegrator::integrate (Src/integrator.h:303-393) for one camera ray
+// The scene behind whit_integrate is a trace policy with three members — closest
+// (Scene::intersect into a HitRec), occluded (Scene::occluded) and surface (the hit's
+// SurfaceInfo; returns the object index, -1 = miss) — and `obj`, the object table that index
+// goes into.  WhitLds: the LDS-resident scene (lscene.h), whatever its kind.
 template <int SCN>
-__device__ v3 whit_integrate(const KParams& P, const LScene& L, v3 ro, v3 rd, WhitCount& C) {
+struct WhitLds {
+    const KParams& P;
+    const LScene& L;
+    const DObj* obj;
+    __device__ __forceinline__ void closest(v3 o, v3 d, HitRec& h) const { closest_l<SCN>(P, L, o, d, h); }
+    __device__ __forceinline__ bool occluded(v3 o, v3 d, float tmax) const { return occluded_l<SCN>(P, L, o, d, tmax); }
+    __device__ __forceinline__ int surface(v3 o, v3 d, const HitRec& h, Surf& S) const {
+        return surface_l<SCN>(L, o, d, h, S);
+    }
+};
+
+// WhittedIntegrator::integrate (Src/integrator.h:303-393) for one camera ray
+template <typename TR>
+__device__ v3 whit_integrate(const KParams& P, const TR& T, v3 ro, v3 rd, WhitCount& C) {
     const v3 sky = mk((float)0.235294, (float)0.67451, (float)0.843137);
     WRay q[kWhitQueue];
     uint32_t head = 0, tail = 0;
@@ -109,18 +130,18 @@ __device__ v3 whit_integrate(const KParams& P, const LScene& L, v3 ro, v3 rd, Wh
             continue;
         }
         HitRec h;
-        closest_l<SCN>(P, L, ray.o, ray.d, h);
+        T.closest(ray.o, ray.d, h);
         ++C.seg;
         Surf S;
-        const int obj = surface_l<SCN>(L, ray.o, ray.d, h, S);
+        const int obj = T.surface(ray.o, ray.d, h, S);
         if (obj < 0) {
             total = total + ray.thr * sky;
             continue;
         }
-        const int mat = L.obj[obj].material;
+        const int mat = T.obj[obj].material;
         if (mat == XRT_MAT_LAMBERT) {
             v3 rad = mk(0, 0, 0);
-            const v3 fr = eval_bxdf(L.obj[obj]);
+            const v3 fr = eval_bxdf(T.obj[obj]);
             for (int l = 0; l < P.n_dlights; ++l) {
                 const DDelta& dl = P.dlights[l];
                 v3 wi;
@@ -136,7 +157,7 @@ __device__ v3 whit_integrate(const KParams& P, const LScene& L, v3 ro, v3 rd, Wh
                     pdf = 1.0f;
                     tmax = kINF;
                 }
-                const bool vis = !occluded_l<SCN>(P, L, S.pos + S.ng * 0.1f, wi, tmax);
+                const bool vis = !T.occluded(S.pos + S.ng * 0.1f, wi, tmax);
                 ++C.shadow;
                 rad = rad + (((fr * (float)vis) * ld3(dl.L)) * smax(0.0f, dot(S.ns, wi))) / pdf;
             }
@@ -172,15 +193,13 @@ __device__ v3 whit_integrate(const KParams& P, const LScene& L, v3 ro, v3 rd, Wh
 // LDS bytes: the scene carve (step_layout), then one stream + sum slice per wave
 __host__ __device__ inline uint32_t whit_wave_off(const KParams& P) { return (step_layout(P).total + 15u) & ~15u; }
 
-template <int SCN>
-__global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __restrict__ work) {
-    extern __shared__ __attribute__((aligned(16))) f4 lds_whit[];
-    char* lb = reinterpret_cast<char*>(lds_whit);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const LScene L = load_lscene(P, lb, tid, kWhitBlock);
-    uint32_t* st = reinterpret_cast<uint32_t*>(lb + whit_wave_off(P) + (tid >> 6) * kWhitWaveLds);
+// One wave's share of the shard: pixels from the counter at `work` until it runs out, the
+// pixel's stream in the wave's LDS slice st (kMT words, then the ordered-sum buffer), the
+// samples' ray trees through the trace policy T.  Both kernels below are this loop.
+template <typename TR>
+__device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint32_t* st, uint32_t* __restrict__ work,
+                                            int lane) {
     float* sum = reinterpret_cast<float*>(st + kMT);
-    __syncthreads();
     unsigned long long w_rays = 0, w_cut = 0, w_refr = 0, w_tir = 0;   // lane totals over this wave's pixels
     for (;;) {
         uint32_t s = 0;
@@ -218,7 +237,7 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
                 const float v = div_h(P, (float)(int)row + rng.next());
                 v3 ro, rd;
                 camera_ray(P, u, v, ro, rd);
-                r = whit_integrate<SCN>(P, L, ro, rd, C) / 1.0f;
+                r = whit_integrate(P, T, ro, rd, C) / 1.0f;
             }
             const uint64_t vm = __ballot(act && !pix_invalid(r));
             nrej += span - (uint32_t)__builtin_popcountll(vm);
@@ -251,6 +270,144 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         if (lane == 0 && v) atomicAdd(P.stats + kStatsWhit + q, v);
     }
+}
+
+template <int SCN>
+__global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __restrict__ work) {
+    extern __shared__ __attribute__((aligned(16))) f4 lds_whit[];
+    char* lb = reinterpret_cast<char*>(lds_whit);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const LScene L = load_lscene(P, lb, tid, kWhitBlock);
+    uint32_t* st = reinterpret_cast<uint32_t*>(lb + whit_wave_off(P) + (tid >> 6) * kWhitWaveLds);
+    __syncthreads();
+    const WhitLds<SCN> T{P, L, L.obj};
+    whit_pixels(P, T, st, work, lane);
+}
+
+// ------------------------------------------------------------ scenes beyond LDS ----
+// k_whitted_bvh: the same wave-per-pixel loop for triangle scenes that do not fit the LDS
+// scene carve but have the triangle BVH xrt_upload_scene builds (bvh.h): every triangle in
+// it (one-level scenes), or the large meshes in it and the small objects beside it (two-level
+// scenes, C4).  Only the three scene accessors differ from k_whitted:
+//
+//   closest   Scene::intersect's result is the lexicographic minimum of (t, original triangle
+//             index) over all triangles (the in-order strict `t < best` scan).  Two-level: the
+//             small objects first, from their LDS copy, in object order with k_trace_2a's
+//             plane and box culls and its strict `t < best` — the (t, index) minimum among
+//             them, their triangles being in index order — carrying the original index
+//             (e2.w); then, if the segment [0, best t] reaches the BVH root (inclusive: an
+//             equal t with a lower index must still be found), bvh_trace starts from that hit
+//             and bvh_leaf's `t < bt || (t == bt && k < bk)` merges the large meshes' triangles
+//             into it: the minimum over both sets, what k_trace_2a + k_trace_deep4 compute.
+//             One-level: bvh_trace alone, from a miss.  The culls are conservative (padded
+//             boxes, the plane argument of DESIGN.md §3), so they never drop a hit the scan
+//             accepts.
+//   occluded  Scene::occluded: the small objects that occlude (count_occ's sign bit: no area
+//             light) first, then bvh_trace<true>, which skips area-light triangles (B.w == 0).
+//   surface   surface<SCN_TRI> (path_common.h) over the global arrays: tri_ng, tri_nrm, the
+//             object index in tri[3 * idx].w; material and albedo from the global object table.
+//
+// Rays arrive as Whitted makes them.  A metal child's direction is not normalised: the slab
+// tests and Moller-Trumbore are consistent under a scale of d (t scales with it).  A NaN
+// direction (normalize of refract's zero vector) must miss everything, and does: its
+// reciprocal is NaN, fminf / fmaxf drop the NaNs so box_overlap and bvh_enter enter every box,
+// plane_away_w's comparison is false, and every ray_tri fails its final `t > eps` — the walk
+// visits the whole tree once and ends as a miss.  Zero-edge triangles of the large meshes
+// are not in the BVH (xrt_upload_scene) and no ray_tri accepts them anyway.
+// The traversal stack (P.bvh_stack entries per thread, 16-bit when the node indices fit) and
+// the top of the tree are in LDS as in k_trace_bvh; the ray ring stays in scratch.
+struct WhitBvhLayout {
+    uint32_t tri, box, plane, stack, wave, total;   // bytes; the top nodes are at 0
+};
+__host__ __device__ inline WhitBvhLayout whit_bvh_layout(const KParams& P) {
+    const uint32_t ntop = (uint32_t)P.bvh_nodes < kBvhTopNodes ? (uint32_t)P.bvh_nodes : kBvhTopNodes;
+    const uint32_t nt = P.two_level ? (uint32_t)P.n_stri : 0u, ns = P.two_level ? (uint32_t)P.n_sobj : 0u;
+    WhitBvhLayout L;
+    L.tri = 64u * ntop;
+    L.box = L.tri + 48u * nt;
+    L.plane = L.box + (uint32_t)sizeof(DObjBox) * ns;
+    L.stack = (L.plane + (uint32_t)sizeof(DObjPlane) * ns + 15u) & ~15u;
+    L.wave = (L.stack + (uint32_t)P.bvh_stack * kWhitBlock * (P.bvh_nodes <= 0x10000 ? 2u : 4u) + 15u) & ~15u;
+    L.total = L.wave + (kWhitBlock / 64) * kWhitWaveLds;
+    return L;
+}
+
+template <bool TWO, typename SE>
+struct WhitBvh {
+    const KParams& P;
+    const f4* top;   // the first ntop nodes (LDS); top[0..3] is the root
+    int ntop;
+    SE* stk;         // this thread's stack, entries kWhitBlock apart
+    const f4* ltri;  // two-level: the small objects' triangles, boxes and planes (LDS)
+    const DObjBox* lbox;
+    const DObjPlane* lpl;
+    const DObj* obj;
+    __device__ __forceinline__ void closest(v3 o, v3 d, HitRec& h) const {
+        h.t = kINF, h.u = h.v = 0.0f, h.code = -1;
+        if (TWO) {
+            const v3 inv = rcp3(d);
+            for (int ob = 0; ob < P.n_sobj; ++ob) {
+                const DObjBox B = lbox[ob];
+                if (plane_away_w(o, d, lpl[ob]) || !box_overlap(o, inv, B, h.t)) continue;
+                const int end = B.first + (B.count_occ & 0x7fffffff);
+                for (int k = B.first; k < end; ++k) {
+                    const f4 E2 = ltri[3 * k + 2];
+                    float t, u, v;
+                    if (ray_tri(o, d, xyz(ltri[3 * k]), xyz(ltri[3 * k + 1]), xyz(E2), t, u, v) && t < h.t)
+                        h.t = t, h.u = u, h.v = v, h.code = __float_as_int(E2.w);
+                }
+            }
+            if (!root_overlap(top[0], top[1], top[2], top[3], o, inv, h.t)) return;
+        }
+        (void)bvh_trace<false, SE, kWhitBlock>(P, top, ntop, stk, o, d, kINF, h.t, h.u, h.v, h.code);
+    }
+    __device__ __forceinline__ bool occluded(v3 o, v3 d, float tmax) const {
+        if (TWO) {
+            const v3 inv = rcp3(d);
+            for (int ob = 0; ob < P.n_sobj; ++ob) {
+                const DObjBox B = lbox[ob];
+                if (B.count_occ >= 0 || plane_away_w(o, d, lpl[ob]) || !box_overlap(o, inv, B, tmax)) continue;
+                const int end = B.first + (B.count_occ & 0x7fffffff);
+                for (int k = B.first; k < end; ++k) {
+                    float t, u, v;
+                    if (ray_tri(o, d, xyz(ltri[3 * k]), xyz(ltri[3 * k + 1]), xyz(ltri[3 * k + 2]), t, u, v) && t < tmax)
+                        return true;
+                }
+            }
+            if (!root_overlap(top[0], top[1], top[2], top[3], o, inv, tmax)) return false;
+        }
+        float bt = kINF, bu = 0.0f, bv = 0.0f;
+        int bk = -1;
+        return bvh_trace<true, SE, kWhitBlock>(P, top, ntop, stk, o, d, tmax, bt, bu, bv, bk);
+    }
+    __device__ __forceinline__ int surface(v3 o, v3 d, const HitRec& h, Surf& S) const {
+        float t1;
+        return xrt::surface<SCN_TRI>(P, 0u, o, d, make_float4(h.t, h.u, h.v, __int_as_float(h.code)), S, t1);
+    }
+};
+
+template <bool TWO, typename SE>
+__global__ __launch_bounds__(kWhitBlock) void k_whitted_bvh(KParams P, uint32_t* __restrict__ work) {
+    extern __shared__ __attribute__((aligned(16))) f4 lds_whit_bvh[];
+    char* lb = reinterpret_cast<char*>(lds_whit_bvh);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const WhitBvhLayout Lo = whit_bvh_layout(P);
+    const int ntop = P.bvh_nodes < (int)kBvhTopNodes ? P.bvh_nodes : (int)kBvhTopNodes;
+    f4* top = lds_whit_bvh;
+    f4* ltri = reinterpret_cast<f4*>(lb + Lo.tri);
+    DObjBox* lbox = reinterpret_cast<DObjBox*>(lb + Lo.box);
+    DObjPlane* lpl = reinterpret_cast<DObjPlane*>(lb + Lo.plane);
+    lds_copy(top, P.bvh_node, 4 * ntop, tid, kWhitBlock);
+    if (TWO) {
+        lds_copy(ltri, P.stri, 3 * P.n_stri, tid, kWhitBlock);
+        lds_copy(lbox, P.sbox, P.n_sobj, tid, kWhitBlock);
+        lds_copy(lpl, P.splane, P.n_sobj, tid, kWhitBlock);
+    }
+    SE* stk = reinterpret_cast<SE*>(lb + Lo.stack) + tid;
+    uint32_t* st = reinterpret_cast<uint32_t*>(lb + Lo.wave + (tid >> 6) * kWhitWaveLds);
+    __syncthreads();
+    const WhitBvh<TWO, SE> T{P, top, ntop, stk, ltri, lbox, lpl, P.objs};
+    whit_pixels(P, T, st, work, lane);
 }
 
 // device self-test (xrt_test_whitted_math): the kernel's own geometry functions
@@ -304,6 +461,41 @@ hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st) {
         case SCN_SPHERE: return whitted_s<SCN_SPHERE>(P, work, st);
         default: return whitted_s<SCN_MIXED>(P, work, st);
     }
+}
+
+size_t whit_bvh_lds_bytes(const KParams& P) { return whit_bvh_layout(P).total; }
+
+bool use_whitted_bvh(const KParams& P) {
+    // a triangle scene with the BVH over its (large meshes') triangles, a tree the stack was
+    // sized for, small objects within the LDS scan's bounds, and an LDS sum this device gives
+    return P.scene_kind == SCN_TRI && P.bvh_node && P.bvh_tri && P.bvh_nodes > 0 && P.bvh_stack > 0 &&
+           P.bvh_stack <= kBvhStack &&
+           (!P.two_level || (P.stri && P.sbox && P.splane && P.n_stri <= kSmallTris && P.n_sobj <= kSmallObjs)) &&
+           whit_bvh_lds_bytes(P) <= kPixLds && whit_bvh_lds_bytes(P) <= P.lds_max;
+}
+
+template <bool TWO, typename SE>
+static hipError_t whitted_bvh_s(const KParams& P, uint32_t* work, hipStream_t st) {
+    const size_t lds = whit_bvh_lds_bytes(P);
+    auto kern = k_whitted_bvh<TWO, SE>;
+    // persistent grid, as whitted_s
+    int dev = 0, ncu = 0, per_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWhitBlock, lds);
+    if (e != hipSuccess) return e;
+    const uint64_t want = ((uint64_t)P.n_slots + kWhitBlock / 64 - 1) / (kWhitBlock / 64);
+    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
+    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(kWhitBlock), lds, st, P, work);
+    return hipGetLastError();
+}
+
+hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st) {
+    if (!use_whitted_bvh(P)) return hipErrorInvalidValue;
+    if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
+    const bool small = P.bvh_nodes <= 0x10000;   // node indices below 2^16: 16-bit stack entries
+    if (P.two_level) return small ? whitted_bvh_s<true, uint16_t>(P, work, st) : whitted_bvh_s<true, uint32_t>(P, work, st);
+    return small ? whitted_bvh_s<false, uint16_t>(P, work, st) : whitted_bvh_s<false, uint32_t>(P, work, st);
 }
 
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st) {

@@ -897,8 +897,9 @@ struct RenderPlan {
     // k_step loop (else k_shade + k_trace); merged: its k_step_merged form; two_level: that
     // kernel with the wave's own BVH walk; step_tri: k_step_tri in place of k_step; spec:
     // k_step_spec in the merged schedule's group layouts, which needs the camera lists.
-    // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it
-    bool pixel, fused, merged, two_level, step_tri, spec, camlist, whitted;
+    // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it, or
+    // (whitted_bvh) k_whitted_bvh for a scene beyond LDS under XRT_FLAG_WHITTED_BVH
+    bool pixel, fused, merged, two_level, step_tri, spec, camlist, whitted, whitted_bvh;
     uint32_t n_part, part_cap;                     // live-list partitions
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
@@ -923,11 +924,14 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p) {
     R.step_tri = R.fused && !R.merged && use_step_tri(P);
     R.spec = R.merged && !R.two_level && !(p->flags & XRT_FLAG_NO_SPEC) && use_step_spec(P);
     R.camlist = R.spec && !exp_env("XRT_NO_CAMLIST");
-    // WhittedIntegrator has one schedule, whatever the flags say (render_impl has refused the
-    // scenes k_whitted cannot hold): one wave per pixel, one lane per sample (whitted.hip)
+    // WhittedIntegrator has one schedule, whatever the schedule flags say (render_impl has
+    // refused the scenes it cannot hold): one wave per pixel, one lane per sample (whitted.hip),
+    // over the LDS scene when it fits, else — XRT_FLAG_WHITTED_BVH — through the triangle BVH
     R.whitted = p->integrator == XRT_INTEGRATOR_WHITTED;
+    R.whitted_bvh = R.whitted && (p->flags & XRT_FLAG_WHITTED_BVH) && !use_whitted(P) && use_whitted_bvh(P);
     if (R.whitted) R.pixel = true, R.two_level = R.merged = R.step_tri = R.spec = R.camlist = false;
-    R.schedule = R.whitted     ? XRT_SCHED_WHITTED
+    R.schedule = R.whitted_bvh ? XRT_SCHED_WHITTED_BVH
+                 : R.whitted   ? XRT_SCHED_WHITTED
                  : R.pixel     ? XRT_SCHED_PIXEL
                  : !R.fused    ? XRT_SCHED_WAVEFRONT
                  : R.two_level ? XRT_SCHED_STEP_BVH
@@ -1091,9 +1095,11 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
         // (zeroed with them)
         uint32_t* work = reinterpret_cast<uint32_t*>(P.stats + kStatsWork);
         const hipError_t e = T.launch(XRT_K_STEP, [&] {
-            return R.whitted ? launch_whitted(P, work, c->stream) : launch_pixel(P, work, c->stream);
+            return R.whitted_bvh ? launch_whitted_bvh(P, work, c->stream)
+                   : R.whitted   ? launch_whitted(P, work, c->stream)
+                                 : launch_pixel(P, work, c->stream);
         });
-        if (e != hipSuccess) return hip_err(c, e, R.whitted ? "k_whitted" : "k_pixel");
+        if (e != hipSuccess) return hip_err(c, e, R.whitted_bvh ? "k_whitted_bvh" : R.whitted ? "k_whitted" : "k_pixel");
     } else {
         HIPCHK(c, T.launch(XRT_K_REFILL, [&] {
             return R.merged ? launch_refill_merged(P, L.req(0), L.req(1), c->stream)
@@ -1220,9 +1226,15 @@ static int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
     if ((rc = grow_slots(c, n)) || (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float))))) return rc;
     float* fb = d_out ? d_out : as<float>(c->fb);   // the caller's device image, or the context's own
     KParams P = render_params(c, p, n, fb);
-    if (p->integrator == XRT_INTEGRATOR_WHITTED && !use_whitted(P))
-        return set_err(c, XRT_ERR_UNSUPPORTED,
-                       "WhittedIntegrator needs a scene that fits the LDS-resident scene carve (not a two-level scene)");
+    if (p->integrator == XRT_INTEGRATOR_WHITTED && !use_whitted(P)) {
+        if (!(p->flags & XRT_FLAG_WHITTED_BVH))
+            return set_err(c, XRT_ERR_UNSUPPORTED,
+                           "WhittedIntegrator needs a scene that fits the LDS-resident scene carve (not a two-level scene)");
+        if (!use_whitted_bvh(P))
+            return set_err(c, XRT_ERR_UNSUPPORTED,
+                           "WhittedIntegrator with XRT_FLAG_WHITTED_BVH: the scene neither fits the LDS-resident scene "
+                           "carve nor has a triangle BVH (a large sphere-only or mixed scene)");
+    }
     const RenderPlan R = plan_render(P, p);
     if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
     P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep;
