@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define XRT_ABI_VERSION 13
+#define XRT_ABI_VERSION 14
 
 /* ---- status codes ---------------------------------------------------------------- */
 enum {
@@ -218,8 +218,10 @@ enum {
     XRT_SCHED_STEP_BVH = 4, XRT_SCHED_PIXEL = 5,
     XRT_SCHED_WHITTED = 6,  /* WhittedIntegrator: one wave per pixel, one lane per sample, the whole
                                ray tree of a sample in its lane (k_whitted; timed as XRT_K_STEP) */
-    XRT_SCHED_WHITTED_BVH = 7   /* the same loop over a triangle scene beyond LDS, its traces through
+    XRT_SCHED_WHITTED_BVH = 7,  /* the same loop over a triangle scene beyond LDS, its traces through
                                    the triangle BVH (k_whitted_bvh, XRT_FLAG_WHITTED_BVH)           */
+    XRT_SCHED_AOV = 8           /* xrt_render_aov: one wave per pixel, one lane per sample, one
+                                   Scene::intersect each (k_aov / k_aov_bvh; timed as XRT_K_STEP)   */
 };
 
 typedef struct {
@@ -321,6 +323,42 @@ int  xrt_render_device(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_ou
  * the legacy default stream) before touching d_rgb_out. */
 int  xrt_render_device_after(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_out, void* hip_stream,
                              xrt_stats* st);
+
+/* ---- first-hit guide buffers (AOVs) --------------------------------------------------- */
+/* Per-pixel guide planes for a denoiser or compositor, taken through the render's own camera
+ * rays: sample k of pixel (row i, col j) takes words 2k, 2k + 1 of the pixel's stream (seed
+ * j + width * i) as its jitter and builds PinholeCamera::sampleRay (Src/camera.h:49-60) as
+ * every schedule does — bit for bit the camera rays of WhittedIntegrator and NormalIntegrator
+ * at the same spp (for the other integrators sample 0 is the same ray).  Each sample is one
+ * Scene::intersect and gives
+ *   albedo [H][W][3]  Lambert: xrt_object.albedo as uploaded; Metal / Glass: (1, 1, 1);
+ *                     XRT_MAT_NONE (emitters, medium boxes): (0, 0, 0)
+ *   normal [H][W][3]  SurfaceInfo::ns as Scene::intersect leaves it
+ *   depth  [H][W]     IntersectInfo::t
+ *   alpha  [H][W]     1
+ *   object [H][W]     int32: the object index (iteration order) of SAMPLE 0 only, -1 on a miss
+ * A miss gives 0 in every float channel.  Every float channel starts at +0.0f, takes each
+ * sample's value in sample order (a miss adds +0.0f) and is divided once by (float)spp; there
+ * is no NaN / Inf / negative rejection.  Mean depth over the hits is depth / alpha (the
+ * caller's division).  Pixels outside the shard are written 0 (object: -1).
+ * A NULL member is a plane that is not wanted: it is neither computed into nor copied; all
+ * five NULL returns XRT_ERR_INVALID.  width, height, spp (> 0), shard_index, shard_count and
+ * XRT_FLAG_TIMING mean what they mean for xrt_render; integrator and max_depth are ignored
+ * (metal and glass objects are accepted), the schedule flags have no effect, and
+ * XRT_FLAG_ACCUMULATE returns XRT_ERR_UNSUPPORTED.  Scenes: those that fit the LDS-resident
+ * scene carve, and triangle scenes beyond it through their triangle BVH (no flag needed);
+ * large sphere-only and mixed scenes return XRT_ERR_UNSUPPORTED, as for WhittedIntegrator.
+ * xrt_stats: samples and path_slots as for a render, segments = samples, shadow_rays = 0,
+ * draws = 2 * samples, rejected = 0, schedule = XRT_SCHED_AOV, the launch under XRT_K_STEP.
+ * A multi-device context shards rows as for a render and assembles every requested plane on
+ * devices[0]. */
+typedef struct { float* albedo; float* normal; float* depth; float* alpha; int32_t* object; } xrt_aov_buffers;
+/* into caller-owned HOST memory; blocks until done */
+int  xrt_render_aov(xrt_ctx* ctx, const xrt_render_params* p, const xrt_aov_buffers* host_out, xrt_stats* st);
+/* into DEVICE pointers on this context's GPU (devices[0]); ordering as xrt_render_device_after:
+ * waits only for the work queued so far on hip_stream (NULL = the legacy default stream) */
+int  xrt_render_aov_device(xrt_ctx* ctx, const xrt_render_params* p, const xrt_aov_buffers* device_out,
+                           void* hip_stream, xrt_stats* st);
 
 /* ---- ray queries: Scene::intersect / Scene::occluded (Src/scene.cpp:190-211) ---------- */
 /* One IntersectInfo (Src/ray.h:23-39) as Scene::intersect leaves a fresh one. */

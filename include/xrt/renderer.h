@@ -24,6 +24,23 @@ protected:
     const Integrator* integrator;
 };
 
+// First-hit guide buffers of a frame (xrt.h, xrt_render_aov), for a denoiser or compositor:
+// sample means of albedo, shading normal, depth (IntersectInfo::t) and coverage over the
+// render's own camera rays, and the object index (Scene iteration order, -1 = miss) of sample
+// 0.  HipRenderer::renderGuides fills the members that have a size — Images of the frame's
+// width x height, vectors of width * height elements in Image::pixels order — and skips empty
+// ones; every sized member must have the size `width` x `height` names.
+struct GuideImages {
+    Image albedo{0, 0}, normal{0, 0};
+    std::vector<float> depth, alpha;
+    std::vector<int32_t> object;
+    uint32_t width = 0, height = 0;   // the frame's size
+    GuideImages() = default;
+    // every plane, sized
+    GuideImages(uint32_t w, uint32_t h)
+        : albedo(w, h), normal(w, h), depth((size_t)w * h), alpha((size_t)w * h), object((size_t)w * h), width(w), height(h) {}
+};
+
 struct xrt_ctx;
 class HipRenderer : public Renderer {
 public:
@@ -35,11 +52,15 @@ public:
     // Errors are reported like the reference reports them (logged; the image is left as
     // rendered so far); lastStatus()/lastError() expose them to callers that care.
     void render(const Scene& scene, Sampler::SamplerType st, Image& image) const override;
+    // The guide buffers of the frame render() would make of `scene` with this camera and
+    // n_samples (the integrator is not consulted); errors as render() reports them.
+    void renderGuides(const Scene& scene, GuideImages& guides) const;
     int lastStatus() const { return m_status; }
     const std::string& lastError() const { return m_error; }
     const xrt_stats& lastStats() const { return m_stats; }
 
 private:
+    int prepare(const Scene& scene) const;   // context, scene, delta lights, camera; XRT_OK or fails with m_error set
     const uint32_t n_samples;
     int m_device;
     std::vector<int> m_devices;   // empty: one GPU (m_device)

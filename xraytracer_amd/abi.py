@@ -17,7 +17,7 @@ if os.environ.get("XRT_LIB"):   # experiment builds (csrc/Makefile `variant` -> 
     _v = os.path.join(HERE, "variants", os.environ["XRT_LIB"])
     LIB_PATH = _v if os.path.exists(_v) else os.path.join(HERE, os.environ["XRT_LIB"])
 
-XRT_ABI_VERSION = 13  # include/xrt.h XRT_ABI_VERSION
+XRT_ABI_VERSION = 14  # include/xrt.h XRT_ABI_VERSION
 XRT_OK = 0
 XRT_OBJ_MESH, XRT_OBJ_SPHERE, XRT_OBJ_BOX = 0, 1, 2
 XRT_LIGHT_QUAD, XRT_LIGHT_TRIANGLE, XRT_LIGHT_SPHERE, XRT_LIGHT_SPHERE_AREA = 0, 1, 2, 3
@@ -30,6 +30,7 @@ XRT_INTEGRATOR_INDIRECT, XRT_INTEGRATOR_NORMAL, XRT_INTEGRATOR_VPT_NEE = 3, 4, 5
 XRT_INTEGRATOR_WHITTED = 6
 XRT_WHITTED_MAX_DEPTH = 4
 XRT_ERR_INVALID, XRT_ERR_UNSUPPORTED = -1, -5
+XRT_ERR_STATE = -3
 XRT_MEDIUM_HETEROGENEOUS, XRT_MEDIUM_HOMOGENEOUS_MIS, XRT_MEDIUM_HOMOGENEOUS_ACHROMATIC, XRT_MEDIUM_HOMOGENEOUS_NOMIS = 0, 1, 2, 3
 XRT_FLAG_TIMING, XRT_FLAG_WAVEFRONT, XRT_FLAG_NO_MERGED, XRT_FLAG_NO_GROUP, XRT_FLAG_ACCUMULATE = 1, 2, 4, 8, 16
 XRT_FLAG_DEEP_SINGLE, XRT_FLAG_DEEP_QUAD, XRT_FLAG_NO_PIXEL = 32, 64, 128
@@ -37,7 +38,10 @@ XRT_FLAG_NO_SPEC = 256
 XRT_FLAG_WHITTED_BVH = 512
 XRT_SCHED_WAVEFRONT, XRT_SCHED_STEP, XRT_SCHED_STEP_TRI, XRT_SCHED_STEP_MERGED, XRT_SCHED_STEP_BVH = 0, 1, 2, 3, 4
 XRT_SCHED_PIXEL, XRT_SCHED_WHITTED, XRT_SCHED_WHITTED_BVH = 5, 6, 7
-SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel", "whitted")
+XRT_SCHED_AOV = 8
+AOV_PLANES = ("albedo", "normal", "depth", "alpha", "object")   # xrt_aov_buffers members, in order
+SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel", "whitted", "whitted_bvh",
+                  "aov")
 XRT_K_SEED, XRT_K_TRACE, XRT_K_SHADE, XRT_K_FINISH, XRT_K_STEP, XRT_K_REFILL, XRT_K_DEEP, XRT_K_COUNT = \
     0, 1, 2, 3, 4, 5, 6, 7
 LAYOUTS = (64, 32, 16, 8, 4)   # xrt_stats.layout_launches: slots per wave
@@ -122,6 +126,11 @@ class XrtStats(C.Structure):
         return d
 
 
+class XrtAovBuffers(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+                ("object", C.c_void_p)]
+
+
 class XrtHit(C.Structure):
     _fields_ = [("hit", C.c_int32), ("object", C.c_int32), ("primitive", C.c_int32), ("t", C.c_float),
                 ("t1", C.c_float), ("position", C.c_float * 3), ("ng", C.c_float * 3), ("ns", C.c_float * 3),
@@ -148,6 +157,9 @@ SIGNATURES = {
     "xrt_render_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.POINTER(XrtStats)]),
     "xrt_render_device_after": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.c_void_p,
                                           C.POINTER(XrtStats)]),
+    "xrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.POINTER(XrtStats)]),
+    "xrt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.c_void_p,
+                                        C.POINTER(XrtStats)]),
     "xrt_hscene_create": (C.c_void_p, []),
     "xrt_hscene_destroy": (None, [C.c_void_p]),
     "xrt_hscene_last_error": (C.c_char_p, [C.c_void_p]),

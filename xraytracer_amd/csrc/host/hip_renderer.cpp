@@ -17,11 +17,12 @@ HipRenderer::~HipRenderer() {
     if (m_ctx) xrt_destroy(m_ctx);
 }
 
-void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image) const {
+int HipRenderer::prepare(const Scene& scene) const {
     auto fail = [&](int rc, const char* what) {
         m_status = rc;
         m_error = std::string(what) + ": " + (m_ctx ? xrt_last_error(m_ctx) : xrt_last_error(nullptr));
         std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+        return rc;
     };
     m_status = XRT_OK;
     m_error.clear();
@@ -45,6 +46,43 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
         for (int c = 0; c < 4; ++c) c2w[4 * r + c] = m[r][c];
     if ((rc = xrt_set_camera(m_ctx, c2w, camera->scale(), camera->aspectRatio())) != XRT_OK)
         return fail(rc, "xrt_set_camera");
+    return XRT_OK;
+}
+
+void HipRenderer::renderGuides(const Scene& scene, GuideImages& g) const {
+    auto fail = [&](int rc, const std::string& msg) {
+        m_status = rc;
+        m_error = msg;
+        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+    };
+    // a member takes part when it has a size, and then it has the frame's
+    const size_t npix = (size_t)g.width * g.height;
+    const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
+    const bool image_ok = (!na || (g.albedo.getWidth() == g.width && g.albedo.getHeight() == g.height)) &&
+                          (!nn || (g.normal.getWidth() == g.width && g.normal.getHeight() == g.height));
+    for (size_t n : {g.depth.size(), g.alpha.size(), g.object.size()})
+        if (npix == 0 || !image_ok || (n && n != npix))
+            return fail(XRT_ERR_INVALID, "renderGuides: every sized member of GuideImages must be width x height");
+    if (prepare(scene) != XRT_OK) return;
+    xrt_render_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = g.width, p.height = g.height, p.spp = n_samples;
+    p.shard_index = 0, p.shard_count = 1;
+    const xrt_aov_buffers out{na ? g.albedo.data() : nullptr, nn ? g.normal.data() : nullptr,
+                              g.depth.empty() ? nullptr : g.depth.data(), g.alpha.empty() ? nullptr : g.alpha.data(),
+                              g.object.empty() ? nullptr : g.object.data()};
+    const int rc = xrt_render_aov(m_ctx, &p, &out, &m_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_render_aov: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image) const {
+    auto fail = [&](int rc, const char* what) {
+        m_status = rc;
+        m_error = std::string(what) + ": " + (m_ctx ? xrt_last_error(m_ctx) : xrt_last_error(nullptr));
+        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+    };
+    int rc = prepare(scene);
+    if (rc != XRT_OK) return;
 
     xrt_render_params p;
     std::memset(&p, 0, sizeof(p));

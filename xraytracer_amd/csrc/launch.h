@@ -76,6 +76,19 @@ hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st);
 bool use_whitted_bvh(const KParams& P);
 size_t whit_bvh_lds_bytes(const KParams& P);
 hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st);
+// First-hit guide buffers (aov.hip, xrt_render_aov): the planes k_aov / k_aov_bvh write for the
+// shard's pixels (device pointers; null = not wanted) and the per-object raw albedo table
+// xrt_upload_scene leaves (3 floats per object).  aov_kernel: 1 = k_aov (the scene fits the
+// LDS carve, use_whitted), 2 = k_aov_bvh (a triangle scene with the BVH, use_whitted_bvh),
+// 0 = neither holds the scene.  launch_aov has launch_pixel's contract (after k_seed; the
+// pixel counter at `work`) but divides and writes its planes itself: no k_finish.
+struct AovOut {
+    float *albedo, *normal, *depth, *alpha;
+    int32_t* object;
+    const float* obj_albedo;
+};
+int aov_kernel(const KParams& P);
+hipError_t launch_aov(const KParams& P, const AovOut& A, uint32_t* work, hipStream_t st);
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned

@@ -35,15 +35,10 @@
 // whit_integrate is instantiated with and in nothing else.
 #include <hip/hip_runtime.h>
 
-#include "bvh_walk.h"
-#include "lds_stream.h"
-#include "lscene.h"
-#include "path_common.h"
+#include "whit_trace.h"
 
 namespace xrt {
 
-constexpr int kWhitBlock = 256;                                       // 4 waves share one LDS scene copy
-constexpr uint32_t kWhitWaveLds = (kMT + 3 * kPixSumStride) * 4;    // stream + ordered-sum buffer
 constexpr uint32_t kWhitQueue = 2u << XRT_WHITTED_MAX_DEPTH;          // rays per lane ring (a power of two)
 constexpr float kWhitIor = 1.3f;   // Src/integrator.h:359,365: the literal 1.3 bound to `const float& ior`
 
@@ -95,21 +90,8 @@ struct WhitCount {
     uint32_t seg = 0, shadow = 0, rays = 0, cut = 0, refr = 0, tir = 0;
 };
 
-// The scene behind whit_integrate is a trace policy with three members — closest
-// (Scene::intersect into a HitRec), occluded (Scene::occluded) and surface (the hit's
-// SurfaceInfo; returns the object index, -1 = miss) — and `obj`, the object table that index
-// goes into.  WhitLds: the LDS-resident scene (lscene.h), whatever its kind.
-template <int SCN>
-struct WhitLds {
-    const KParams& P;
-    const LScene& L;
-    const DObj* obj;
-    __device__ __forceinline__ void closest(v3 o, v3 d, HitRec& h) const { closest_l<SCN>(P, L, o, d, h); }
-    __device__ __forceinline__ bool occluded(v3 o, v3 d, float tmax) const { return occluded_l<SCN>(P, L, o, d, tmax); }
-    __device__ __forceinline__ int surface(v3 o, v3 d, const HitRec& h, Surf& S) const {
-        return surface_l<SCN>(L, o, d, h, S);
-    }
-};
+// The scene behind whit_integrate is a trace policy (whit_trace.h): closest, occluded, surface
+// and the object table `obj`.
 
 // WhittedIntegrator::integrate (Src/integrator.h:303-393) for one camera ray
 template <typename TR>
@@ -189,9 +171,6 @@ __device__ v3 whit_integrate(const KParams& P, const TR& T, v3 ro, v3 rd, WhitCo
     }
     return total;
 }
-
-// LDS bytes: the scene carve (step_layout), then one stream + sum slice per wave
-__host__ __device__ inline uint32_t whit_wave_off(const KParams& P) { return (step_layout(P).total + 15u) & ~15u; }
 
 // One wave's share of the shard: pixels from the counter at `work` until it runs out, the
 // pixel's stream in the wave's LDS slice st (kMT words, then the ordered-sum buffer), the
@@ -315,77 +294,8 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
 // visits the whole tree once and ends as a miss.  Zero-edge triangles of the large meshes
 // are not in the BVH (xrt_upload_scene) and no ray_tri accepts them anyway.
 // The traversal stack (P.bvh_stack entries per thread, 16-bit when the node indices fit) and
-// the top of the tree are in LDS as in k_trace_bvh; the ray ring stays in scratch.
-struct WhitBvhLayout {
-    uint32_t tri, box, plane, stack, wave, total;   // bytes; the top nodes are at 0
-};
-__host__ __device__ inline WhitBvhLayout whit_bvh_layout(const KParams& P) {
-    const uint32_t ntop = (uint32_t)P.bvh_nodes < kBvhTopNodes ? (uint32_t)P.bvh_nodes : kBvhTopNodes;
-    const uint32_t nt = P.two_level ? (uint32_t)P.n_stri : 0u, ns = P.two_level ? (uint32_t)P.n_sobj : 0u;
-    WhitBvhLayout L;
-    L.tri = 64u * ntop;
-    L.box = L.tri + 48u * nt;
-    L.plane = L.box + (uint32_t)sizeof(DObjBox) * ns;
-    L.stack = (L.plane + (uint32_t)sizeof(DObjPlane) * ns + 15u) & ~15u;
-    L.wave = (L.stack + (uint32_t)P.bvh_stack * kWhitBlock * (P.bvh_nodes <= 0x10000 ? 2u : 4u) + 15u) & ~15u;
-    L.total = L.wave + (kWhitBlock / 64) * kWhitWaveLds;
-    return L;
-}
-
-template <bool TWO, typename SE>
-struct WhitBvh {
-    const KParams& P;
-    const f4* top;   // the first ntop nodes (LDS); top[0..3] is the root
-    int ntop;
-    SE* stk;         // this thread's stack, entries kWhitBlock apart
-    const f4* ltri;  // two-level: the small objects' triangles, boxes and planes (LDS)
-    const DObjBox* lbox;
-    const DObjPlane* lpl;
-    const DObj* obj;
-    __device__ __forceinline__ void closest(v3 o, v3 d, HitRec& h) const {
-        h.t = kINF, h.u = h.v = 0.0f, h.code = -1;
-        if (TWO) {
-            const v3 inv = rcp3(d);
-            for (int ob = 0; ob < P.n_sobj; ++ob) {
-                const DObjBox B = lbox[ob];
-                if (plane_away_w(o, d, lpl[ob]) || !box_overlap(o, inv, B, h.t)) continue;
-                const int end = B.first + (B.count_occ & 0x7fffffff);
-                for (int k = B.first; k < end; ++k) {
-                    const f4 E2 = ltri[3 * k + 2];
-                    float t, u, v;
-                    if (ray_tri(o, d, xyz(ltri[3 * k]), xyz(ltri[3 * k + 1]), xyz(E2), t, u, v) && t < h.t)
-                        h.t = t, h.u = u, h.v = v, h.code = __float_as_int(E2.w);
-                }
-            }
-            if (!root_overlap(top[0], top[1], top[2], top[3], o, inv, h.t)) return;
-        }
-        (void)bvh_trace<false, SE, kWhitBlock>(P, top, ntop, stk, o, d, kINF, h.t, h.u, h.v, h.code);
-    }
-    __device__ __forceinline__ bool occluded(v3 o, v3 d, float tmax) const {
-        if (TWO) {
-            const v3 inv = rcp3(d);
-            for (int ob = 0; ob < P.n_sobj; ++ob) {
-                const DObjBox B = lbox[ob];
-                if (B.count_occ >= 0 || plane_away_w(o, d, lpl[ob]) || !box_overlap(o, inv, B, tmax)) continue;
-                const int end = B.first + (B.count_occ & 0x7fffffff);
-                for (int k = B.first; k < end; ++k) {
-                    float t, u, v;
-                    if (ray_tri(o, d, xyz(ltri[3 * k]), xyz(ltri[3 * k + 1]), xyz(ltri[3 * k + 2]), t, u, v) && t < tmax)
-                        return true;
-                }
-            }
-            if (!root_overlap(top[0], top[1], top[2], top[3], o, inv, tmax)) return false;
-        }
-        float bt = kINF, bu = 0.0f, bv = 0.0f;
-        int bk = -1;
-        return bvh_trace<true, SE, kWhitBlock>(P, top, ntop, stk, o, d, tmax, bt, bu, bv, bk);
-    }
-    __device__ __forceinline__ int surface(v3 o, v3 d, const HitRec& h, Surf& S) const {
-        float t1;
-        return xrt::surface<SCN_TRI>(P, 0u, o, d, make_float4(h.t, h.u, h.v, __int_as_float(h.code)), S, t1);
-    }
-};
-
+// the top of the tree are in LDS as in k_trace_bvh; the ray ring stays in scratch.  The layout
+// and the policy (WhitBvhLayout, WhitBvh) are in whit_trace.h.
 template <bool TWO, typename SE>
 __global__ __launch_bounds__(kWhitBlock) void k_whitted_bvh(KParams P, uint32_t* __restrict__ work) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_whit_bvh[];

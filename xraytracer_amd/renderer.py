@@ -118,6 +118,50 @@ class HipRenderer:
         self.stats = st
         return img
 
+    _AOV_SHAPES = {"albedo": (3,), "normal": (3,), "depth": (), "alpha": (), "object": ()}
+
+    def render_aov(self, scene: SceneBundle, width: int, height: int,
+                   planes=("albedo", "normal", "depth", "alpha", "object"), **kw) -> dict:
+        """First-hit guide buffers (xrt_render_aov) through the render's own jittered camera
+        rays at self.spp: a dict of the requested planes — albedo, normal (H, W, 3), depth,
+        alpha (H, W) float32 sample means, object (H, W) int32 (sample 0's object, -1 = miss).
+        Mean depth over the hits is depth / alpha.  kw: shard_index, shard_count, timing; the
+        integrator and the schedule keywords have no effect."""
+        planes = tuple(planes)
+        bad = [n for n in planes if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        out = {n: np.zeros((height, width) + self._AOV_SHAPES[n], np.int32 if n == "object" else np.float32)
+               for n in planes}
+        bufs = abi.XrtAovBuffers(**{n: a.ctypes.data for n, a in out.items()})
+        st = abi.XrtStats()
+        self._check(self._lib.xrt_render_aov(self.ctx, C.byref(p), C.byref(bufs), C.byref(st)), "xrt_render_aov")
+        self.stats = st
+        return out
+
+    def render_aov_device(self, scene: SceneBundle, width: int, height: int, ptrs: dict, after_stream=None, **kw):
+        """Guide buffers into device memory (xrt_render_aov_device): ptrs maps plane names to
+        device pointers (torch tensor .data_ptr()) of H*W*3 float32 (albedo, normal), H*W float32
+        (depth, alpha) or H*W int32 (object); planes left out are not computed into.
+        after_stream: the HIP stream whose queued work must finish before the buffers are
+        overwritten (torch.cuda.current_stream().cuda_stream; None = the legacy default stream).
+        Returns the stats when the planes are complete."""
+        bad = [n for n in ptrs if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        bufs = abi.XrtAovBuffers(**{n: int(v) for n, v in ptrs.items() if v})
+        st = abi.XrtStats()
+        self._check(self._lib.xrt_render_aov_device(self.ctx, C.byref(p), C.byref(bufs), C.c_void_p(after_stream or None),
+                                                    C.byref(st)), "xrt_render_aov_device")
+        self.stats = st
+        return st
+
     def query(self, scene: SceneBundle, rays: np.ndarray, tmax=None, occluded: bool = False):
         """Scene::intersect (or, with occluded=True, Scene::occluded(ray, tmax)) for rays
         (n, 6) = origin, direction, on the GPU with the render's trace kernels (xrt_query).
