@@ -360,6 +360,65 @@ int  xrt_render_aov(xrt_ctx* ctx, const xrt_render_params* p, const xrt_aov_buff
 int  xrt_render_aov_device(xrt_ctx* ctx, const xrt_render_params* p, const xrt_aov_buffers* device_out,
                            void* hip_stream, xrt_stats* st);
 
+/* ---- denoiser: edge-avoiding a-trous filter over a frame and its guide buffers -------- */
+/* Dammertz et al. 2010: `iterations` passes of a 5 x 5 B3-spline kernel with tap spacing 1, 2, 4,
+ * ... pixels; each tap is weighted by how far colour, shading normal, depth and albedo are from the
+ * centre pixel's and cut to zero across an object-id boundary.  There is no albedo demodulation
+ * (albedo is constant per object and the object stop already separates objects).
+ * Inputs, in Image::pixels order: color [H][W][3] and the planes xrt_render_aov makes — albedo,
+ * normal [H][W][3], depth [H][W], object [H][W] int32; alpha is ignored.  A NULL plane behaves
+ * exactly as a plane of zeros (object: all 0), a NULL `guides` as all planes NULL.
+ * The arithmetic is IEEE float32, one rounding per operation, no fused multiply-add:
+ *   inv_x = sigma_x > 0 ? 1.0f / (sigma_x * sigma_x) : +0.0f      (x = color, normal, depth, albedo)
+ *   iteration i = 0 .. iterations - 1, tap spacing s = 1 << i:
+ *     kc = inv_color * (float)(1u << 2 i)            the colour stop tightens by 2 per iteration
+ *     kz = inv_depth * (1.0f / (float)(1u << 2 i))   sigma_depth: the depth change tolerated per
+ *                                                    step of tap spacing, in world units
+ *     kn = inv_normal, ka = inv_albedo
+ *     for pixel p, with c the iteration's input colour (the caller's, then the previous output):
+ *       acc = (+0, +0, +0); ws = +0
+ *       for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = p + s (dx, dy), q inside the image:
+ *         d2c = (dc.x dc.x + dc.y dc.y) + dc.z dc.z,  dc = c[p] - c[q]   (d2n, d2a alike)
+ *         d2z = dz dz,  dz = depth[p] - depth[q]
+ *         e = ((d2c kc + d2n kn) + d2z kz) + d2a ka
+ *         w = expf(-e) * (h[dy + 2] h[dx + 2]),  h = {1/16, 1/4, 3/8, 1/4, 1/16}, expf glibc's
+ *         if object[p] != object[q]: w = +0
+ *         acc.ch = acc.ch + c[q].ch w;  ws = ws + w
+ *       out[p].ch = acc.ch / ws
+ * The centre tap runs at its place in the loop (e = +0, w = 9/64), so ws > 0 for finite input.
+ * Input must be finite; a non-finite value in a pixel's window leaves that pixel unspecified.
+ * out == color is allowed; partial overlap is unspecified.
+ * color NULL: the framebuffer of the context's last xrt_render, as xrt_tonemap reads it
+ * (XRT_ERR_STATE when there is none of that size).  No scene or camera is needed.  A multi-device
+ * context filters on devices[0], where frames and planes are assembled.  XRT_ERR_INVALID: NULL
+ * ctx, params or out; width or height 0; iterations 0 or above XRT_DENOISE_MAX_ITERATIONS. */
+#define XRT_DENOISE_MAX_ITERATIONS 6
+#define XRT_DENOISE_TILED_ITERATIONS 2   /* the first n iterations (steps 1, 2) take the LDS-tiled kernel */
+enum {
+    XRT_DENOISE_TIMING = 1u,   /* time the launches with HIP events (xrt_denoise_stats.kernel_ms) */
+    XRT_DENOISE_NO_TILE = 2u   /* every iteration through the direct kernel; same results          */
+};
+typedef struct {
+    uint32_t width, height, iterations;
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;   /* <= 0: the term is off */
+    uint32_t flags;            /* XRT_DENOISE_*                                                     */
+} xrt_denoise_params;
+typedef struct {
+    double wall_ms;            /* host wall clock of the call                                       */
+    double kernel_ms;          /* HIP-event time over all launches (XRT_DENOISE_TIMING), else 0     */
+    uint32_t launches;         /* the prepass and one per iteration                                 */
+    uint32_t tiled_iterations, direct_iterations;   /* iterations per kernel                        */
+    uint32_t reserved;
+} xrt_denoise_stats;
+/* caller-owned HOST memory; blocks until done */
+int  xrt_denoise(xrt_ctx* ctx, const xrt_denoise_params* p, const float* color, const xrt_aov_buffers* guides,
+                 float* out, xrt_denoise_stats* st);
+/* DEVICE pointers on this context's GPU (devices[0]); ordering as xrt_render_aov_device: waits only
+ * for the work queued so far on hip_stream (NULL = the legacy default stream) and returns when
+ * d_out is complete */
+int  xrt_denoise_device(xrt_ctx* ctx, const xrt_denoise_params* p, const float* d_color,
+                        const xrt_aov_buffers* d_guides, float* d_out, void* hip_stream, xrt_denoise_stats* st);
+
 /* ---- ray queries: Scene::intersect / Scene::occluded (Src/scene.cpp:190-211) ---------- */
 /* One IntersectInfo (Src/ray.h:23-39) as Scene::intersect leaves a fresh one. */
 typedef struct {

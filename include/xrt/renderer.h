@@ -41,6 +41,17 @@ struct GuideImages {
         : albedo(w, h), normal(w, h), depth((size_t)w * h), alpha((size_t)w * h), object((size_t)w * h), width(w), height(h) {}
 };
 
+// The edge-avoiding a-trous filter's settings (xrt.h, xrt_denoise): passes of the 5 x 5 kernel
+// with tap spacing 1, 2, 4, ..., and the four edge-stopping widths; a sigma <= 0 turns its term
+// off.  sigma_depth is the depth change tolerated per step of tap spacing in the scene's world
+// units, so it has no scene-independent default and starts off.  tile = false sends every
+// iteration through the direct kernel (same results).
+struct DenoiseSettings {
+    uint32_t iterations = 3;
+    float sigma_color = 2.0f, sigma_normal = 0.5f, sigma_depth = 0.0f, sigma_albedo = 0.2f;
+    bool tile = true, timing = false;
+};
+
 struct xrt_ctx;
 class HipRenderer : public Renderer {
 public:
@@ -55,11 +66,17 @@ public:
     // The guide buffers of the frame render() would make of `scene` with this camera and
     // n_samples (the integrator is not consulted); errors as render() reports them.
     void renderGuides(const Scene& scene, GuideImages& guides) const;
+    // Filters `image` in place over the planes of `guides` that have a size (the others are
+    // passed as NULL: planes of zeros; alpha is not read).  Needs no scene; creates the context
+    // if no call has yet.  Errors as render() reports them.
+    void denoise(Image& image, const GuideImages& guides, const DenoiseSettings& settings = {}) const;
     int lastStatus() const { return m_status; }
     const std::string& lastError() const { return m_error; }
     const xrt_stats& lastStats() const { return m_stats; }
+    const xrt_denoise_stats& lastDenoiseStats() const { return m_denoise_stats; }
 
 private:
+    int context() const;                     // creates the context on first use; XRT_OK or fails with m_error set
     int prepare(const Scene& scene) const;   // context, scene, delta lights, camera; XRT_OK or fails with m_error set
     const uint32_t n_samples;
     int m_device;
@@ -68,4 +85,5 @@ private:
     mutable int m_status = 0;
     mutable std::string m_error;
     mutable xrt_stats m_stats{};
+    mutable xrt_denoise_stats m_denoise_stats{};
 };

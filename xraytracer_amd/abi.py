@@ -40,6 +40,10 @@ XRT_SCHED_WAVEFRONT, XRT_SCHED_STEP, XRT_SCHED_STEP_TRI, XRT_SCHED_STEP_MERGED, 
 XRT_SCHED_PIXEL, XRT_SCHED_WHITTED, XRT_SCHED_WHITTED_BVH = 5, 6, 7
 XRT_SCHED_AOV = 8
 AOV_PLANES = ("albedo", "normal", "depth", "alpha", "object")   # xrt_aov_buffers members, in order
+XRT_DENOISE_MAX_ITERATIONS = 6
+XRT_DENOISE_TILED_ITERATIONS = 2   # include/xrt.h: the first n iterations take the LDS-tiled kernel
+XRT_DENOISE_TIMING, XRT_DENOISE_NO_TILE = 1, 2
+DENOISE_PLANES = ("albedo", "normal", "depth", "object")   # the guide planes xrt_denoise reads
 SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel", "whitted", "whitted_bvh",
                   "aov")
 XRT_K_SEED, XRT_K_TRACE, XRT_K_SHADE, XRT_K_FINISH, XRT_K_STEP, XRT_K_REFILL, XRT_K_DEEP, XRT_K_COUNT = \
@@ -131,6 +135,17 @@ class XrtAovBuffers(C.Structure):
                 ("object", C.c_void_p)]
 
 
+class XrtDenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
+
+
+class XrtDenoiseStats(C.Structure):
+    _fields_ = [("wall_ms", C.c_double), ("kernel_ms", C.c_double), ("launches", C.c_uint32),
+                ("tiled_iterations", C.c_uint32), ("direct_iterations", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class XrtHit(C.Structure):
     _fields_ = [("hit", C.c_int32), ("object", C.c_int32), ("primitive", C.c_int32), ("t", C.c_float),
                 ("t1", C.c_float), ("position", C.c_float * 3), ("ng", C.c_float * 3), ("ns", C.c_float * 3),
@@ -160,6 +175,10 @@ SIGNATURES = {
     "xrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.POINTER(XrtStats)]),
     "xrt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.c_void_p,
                                         C.POINTER(XrtStats)]),
+    "xrt_denoise": (C.c_int, [C.c_void_p, C.POINTER(XrtDenoiseParams), C.c_void_p, C.POINTER(XrtAovBuffers), C.c_void_p,
+                              C.POINTER(XrtDenoiseStats)]),
+    "xrt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(XrtDenoiseParams), C.c_void_p, C.POINTER(XrtAovBuffers),
+                                     C.c_void_p, C.c_void_p, C.POINTER(XrtDenoiseStats)]),
     "xrt_hscene_create": (C.c_void_p, []),
     "xrt_hscene_destroy": (None, [C.c_void_p]),
     "xrt_hscene_last_error": (C.c_char_p, [C.c_void_p]),

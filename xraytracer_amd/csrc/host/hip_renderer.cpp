@@ -17,6 +17,20 @@ HipRenderer::~HipRenderer() {
     if (m_ctx) xrt_destroy(m_ctx);
 }
 
+int HipRenderer::context() const {
+    m_status = XRT_OK;
+    m_error.clear();
+    if (m_ctx) return XRT_OK;
+    const int rc = m_devices.size() > 1 ? xrt_create_multi(m_devices.data(), (int)m_devices.size(), &m_ctx)
+                                        : xrt_create(m_device, &m_ctx);
+    if (rc != XRT_OK) {
+        m_status = rc;
+        m_error = std::string("xrt_create: ") + xrt_last_error(nullptr);
+        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+    }
+    return rc;
+}
+
 int HipRenderer::prepare(const Scene& scene) const {
     auto fail = [&](int rc, const char* what) {
         m_status = rc;
@@ -24,15 +38,10 @@ int HipRenderer::prepare(const Scene& scene) const {
         std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
         return rc;
     };
-    m_status = XRT_OK;
-    m_error.clear();
-    if (!m_ctx) {
-        const int rc = m_devices.size() > 1 ? xrt_create_multi(m_devices.data(), (int)m_devices.size(), &m_ctx)
-                                            : xrt_create(m_device, &m_ctx);
-        if (rc != XRT_OK) return fail(rc, "xrt_create");
-    }
+    int rc = context();
+    if (rc != XRT_OK) return rc;
     xrt_scene_desc desc;
-    int rc = scene.flatten(&desc);
+    rc = scene.flatten(&desc);
     if (rc != XRT_OK) return fail(rc, "Scene::flatten");
     if ((rc = xrt_upload_scene(m_ctx, &desc)) != XRT_OK) return fail(rc, "xrt_upload_scene");
 
@@ -73,6 +82,34 @@ void HipRenderer::renderGuides(const Scene& scene, GuideImages& g) const {
                               g.object.empty() ? nullptr : g.object.data()};
     const int rc = xrt_render_aov(m_ctx, &p, &out, &m_stats);
     if (rc != XRT_OK) fail(rc, std::string("xrt_render_aov: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::denoise(Image& image, const GuideImages& g, const DenoiseSettings& s) const {
+    auto fail = [&](int rc, const std::string& msg) {
+        m_status = rc;
+        m_error = msg;
+        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+    };
+    // a guide plane takes part when it has a size, and then it has the image's
+    const uint32_t w = image.getWidth(), h = image.getHeight();
+    const size_t npix = (size_t)w * h;
+    const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
+    if ((na && (g.albedo.getWidth() != w || g.albedo.getHeight() != h)) ||
+        (nn && (g.normal.getWidth() != w || g.normal.getHeight() != h)) || (!g.depth.empty() && g.depth.size() != npix) ||
+        (!g.object.empty() && g.object.size() != npix))
+        return fail(XRT_ERR_INVALID, "denoise: every sized member of GuideImages must have the image's size");
+    if (context() != XRT_OK) return;
+    xrt_denoise_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = w, p.height = h, p.iterations = s.iterations;
+    p.sigma_color = s.sigma_color, p.sigma_normal = s.sigma_normal, p.sigma_depth = s.sigma_depth, p.sigma_albedo = s.sigma_albedo;
+    p.flags = (s.timing ? XRT_DENOISE_TIMING : 0u) | (s.tile ? 0u : XRT_DENOISE_NO_TILE);
+    // xrt_aov_buffers serves outputs elsewhere; the filter only reads through it
+    const xrt_aov_buffers in{na ? const_cast<float*>(g.albedo.data()) : nullptr, nn ? const_cast<float*>(g.normal.data()) : nullptr,
+                             g.depth.empty() ? nullptr : const_cast<float*>(g.depth.data()), nullptr,
+                             g.object.empty() ? nullptr : const_cast<int32_t*>(g.object.data())};
+    const int rc = xrt_denoise(m_ctx, &p, image.data(), &in, image.data(), &m_denoise_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_denoise: ") + xrt_last_error(m_ctx));
 }
 
 void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image) const {

@@ -89,6 +89,28 @@ struct AovOut {
 };
 int aov_kernel(const KParams& P);
 hipError_t launch_aov(const KParams& P, const AovOut& A, uint32_t* work, hipStream_t st);
+// Edge-avoiding a-trous filter (denoise.hip, xrt_denoise).  launch_denoise_pack gathers the
+// caller's planes (device pointers; color is required, a null guide plane packs as zeros) into
+// the per-pixel records col = {c.rgb, depth}, nrm = {n.xyz, object bits}, alb = {albedo.rgb, 0}.
+// launch_denoise_iter runs one iteration with tap spacing `step` pixels from cin: into the col
+// records cout, or, when out3 is set (the last iteration), into that packed float3 image.
+// tiled: through the LDS-tiled kernel, which exists for the steps denoise_has_tiled names; both
+// kernels give the same bits.
+struct DenoiseK {
+    float kc, kn, kz, ka;   // the iteration's factors on the squared colour / normal / depth / albedo distance
+};
+struct DenoiseIter {
+    const f4 *cin, *nrm, *alb;
+    f4* cout;
+    float* out3;
+    uint32_t width, height;
+    int step;
+    DenoiseK K;
+};
+hipError_t launch_denoise_pack(const float* color, const float* albedo, const float* normal, const float* depth,
+                               const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb, hipStream_t st);
+bool denoise_has_tiled(int step);
+hipError_t launch_denoise_iter(const DenoiseIter& I, bool tiled, hipStream_t st);
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned

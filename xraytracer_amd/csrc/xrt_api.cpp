@@ -75,6 +75,9 @@ struct xrt_ctx {
     // guide buffers (xrt_render_aov): per object the albedo as uploaded (3 floats; DObj keeps
     // only albedo / PI), and the context's own planes (host output, sub-contexts of a multi render)
     DevBuf obj_albedo, aov;
+    // xrt_denoise: the per-pixel records (two colour buffers, normal, albedo: 16 B each), then for
+    // the host entry point the staged input planes and the output image
+    DevBuf denoise;
 };
 
 namespace {
@@ -260,7 +263,7 @@ void xrt_destroy(xrt_ctx* c) {
     free_buf(c->stri), free_buf(c->sbox), free_buf(c->splane), free_buf(c->bvh4), free_buf(c->deep);
     free_buf(c->stage), free_buf(c->q_rays), free_buf(c->q_tmax), free_buf(c->q_out);
     free_buf(c->brick_table), free_buf(c->brick_data), free_buf(c->corners), free_buf(c->camlist);
-    free_buf(c->dlights), free_buf(c->obj_albedo), free_buf(c->aov);
+    free_buf(c->dlights), free_buf(c->obj_albedo), free_buf(c->aov), free_buf(c->denoise);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->poll_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1657,6 +1660,94 @@ int xrt_render_aov_device(xrt_ctx* c, const xrt_render_params* p, const xrt_aov_
     if (rc) return rc;
     if (!c->subs.empty()) return aov_multi(c, p, device_out, nullptr, st, 2, (hipStream_t)hip_stream);
     return aov_one(c, p, *device_out, st, 2, (hipStream_t)hip_stream);
+}
+
+// ------------------------------------------------------------------ denoiser ----
+// xrt_denoise / xrt_denoise_device (denoise.hip): the prepass packs the planes into records, then
+// one launch per iteration, ping-ponging the colour records; the last writes `out`.
+// host: color / guides / out are host memory, staged through the context's buffer.
+// wait_stream: the device entry point's ordering (xrt_render_aov_device's).
+static int denoise_impl(xrt_ctx* m, const xrt_denoise_params* p, const float* color, const xrt_aov_buffers* guides,
+                        float* out, bool host, hipStream_t wait_stream, xrt_denoise_stats* st) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (!m || !p || !out) return set_err(m, XRT_ERR_INVALID, "xrt_denoise: null argument");
+    if (p->width == 0 || p->height == 0) return set_err(m, XRT_ERR_INVALID, "xrt_denoise: bad image size");
+    if (p->iterations == 0 || p->iterations > XRT_DENOISE_MAX_ITERATIONS)
+        return set_err(m, XRT_ERR_INVALID, "xrt_denoise: iterations must be 1 .. XRT_DENOISE_MAX_ITERATIONS");
+    xrt_ctx* c = m->subs.empty() ? m : m->subs[0];   // multi-GPU context: where frames and planes are assembled
+    auto fail = [&](int rc) { return c == m ? rc : multi_fail(m, c, rc, "xrt_denoise"); };
+    const size_t npix = (size_t)p->width * p->height;
+    if (!color && (!c->fb.p || npix * 3 * sizeof(float) > c->fb.bytes))
+        return set_err(m, XRT_ERR_STATE, "xrt_denoise: no framebuffer of that size (render first)");
+    HIPCHK(m, hipSetDevice(c->device));
+    if (!host) {
+        HIPCHK(m, hipEventRecord(c->wait_ev, wait_stream));
+        HIPCHK(m, hipStreamWaitEvent(c->stream, c->wait_ev, 0));
+    }
+    const xrt_aov_buffers none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const xrt_aov_buffers& g = guides ? *guides : none;
+    // records: col[2], nrm, alb; host staging behind them: color 3, albedo 3, normal 3, depth 1, object 1, out 3
+    int rc = ensure(c, c->denoise, npix * (4 * sizeof(f4) + (host ? 14 * sizeof(float) : 0)));
+    if (rc) return fail(rc);
+    f4* rec = as<f4>(c->denoise);
+    f4 *col[2] = {rec, rec + npix}, *nrm = rec + 2 * npix, *alb = rec + 3 * npix;
+    const float* d_color = color ? color : as<float>(c->fb);
+    const float *d_albedo = g.albedo, *d_normal = g.normal, *d_depth = g.depth;
+    const int32_t* d_object = g.object;
+    float* d_out = out;
+    if (host) {
+        float* s = reinterpret_cast<float*>(rec + 4 * npix);
+        auto stage = [&](const void* src, size_t off, size_t ch) -> const float* {
+            if (!src) return nullptr;
+            return hipMemcpyAsync(s + off * npix, src, npix * ch * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess
+                       ? s + off * npix : nullptr;
+        };
+        if (color && !(d_color = stage(color, 0, 3))) return fail(set_err(c, XRT_ERR_HIP, "xrt_denoise: copy of color"));
+        d_albedo = stage(g.albedo, 3, 3), d_normal = stage(g.normal, 6, 3), d_depth = stage(g.depth, 9, 1);
+        d_object = reinterpret_cast<const int32_t*>(stage(g.object, 10, 1));
+        if ((g.albedo && !d_albedo) || (g.normal && !d_normal) || (g.depth && !d_depth) || (g.object && !d_object))
+            return fail(set_err(c, XRT_ERR_HIP, "xrt_denoise: copy of a guide plane"));
+        d_out = s + 11 * npix;
+    }
+    const float sig[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
+    float inv[4];
+    for (int k = 0; k < 4; ++k) inv[k] = sig[k] > 0.0f ? 1.0f / (sig[k] * sig[k]) : 0.0f;
+    xrt_stats S{};
+    xrt_denoise_stats D{};
+    LaunchTimer T{c, S, (p->flags & XRT_DENOISE_TIMING) != 0, {}, {}};
+    hipError_t e = T.launch(XRT_K_STEP, [&] {
+        return launch_denoise_pack(d_color, d_albedo, d_normal, d_depth, d_object, npix, col[0], nrm, alb, c->stream);
+    });
+    if (e != hipSuccess) return fail(hip_err(c, e, "k_dn_pack"));
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        const float scale = (float)(1u << (2 * i));
+        const bool last = i + 1 == p->iterations;
+        const bool tiled = !(p->flags & XRT_DENOISE_NO_TILE) && i < XRT_DENOISE_TILED_ITERATIONS && denoise_has_tiled(1 << i);
+        const DenoiseIter I{col[i & 1], nrm, alb, last ? nullptr : col[(i + 1) & 1], last ? d_out : nullptr,
+                            p->width, p->height, 1 << i, DenoiseK{inv[0] * scale, inv[1], inv[2] * (1.0f / scale), inv[3]}};
+        e = T.launch(XRT_K_STEP, [&] { return launch_denoise_iter(I, tiled, c->stream); });
+        if (e != hipSuccess) return fail(hip_err(c, e, tiled ? "k_dn_tiled" : "k_dn_direct"));
+        (tiled ? D.tiled_iterations : D.direct_iterations)++;
+    }
+    if (host) e = hipMemcpyAsync(out, d_out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(hip_err(c, e, "xrt_denoise"));
+    T.read_out();
+    D.kernel_ms = S.kernel_ms[XRT_K_STEP];
+    D.launches = (uint32_t)S.launches[XRT_K_STEP];
+    D.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (st) *st = D;
+    return XRT_OK;
+}
+
+int xrt_denoise(xrt_ctx* c, const xrt_denoise_params* p, const float* color, const xrt_aov_buffers* guides, float* out,
+                xrt_denoise_stats* st) {
+    return denoise_impl(c, p, color, guides, out, true, nullptr, st);
+}
+
+int xrt_denoise_device(xrt_ctx* c, const xrt_denoise_params* p, const float* d_color, const xrt_aov_buffers* d_guides,
+                       float* d_out, void* hip_stream, xrt_denoise_stats* st) {
+    return denoise_impl(c, p, d_color, d_guides, d_out, false, (hipStream_t)hip_stream, st);
 }
 
 // Scene::intersect / Scene::occluded (Src/scene.cpp:190-211) for caller rays, on the GPU

@@ -162,6 +162,64 @@ class HipRenderer:
         self.stats = st
         return st
 
+    @staticmethod
+    def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing):
+        return abi.XrtDenoiseParams(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo,
+                                    (abi.XRT_DENOISE_TIMING if timing else 0) | (0 if tile else abi.XRT_DENOISE_NO_TILE))
+
+    def denoise(self, color, guides: dict, iterations=3, sigma_color=2.0, sigma_normal=0.5, sigma_depth=0.0,
+                sigma_albedo=0.2, tile=True, timing=False, out=None, width=None, height=None) -> np.ndarray:
+        """Edge-avoiding a-trous filter (xrt_denoise) of the (H, W, 3) float32 frame `color` over
+        the guide planes of `guides` — albedo, normal, depth, object as render_aov returns them;
+        alpha is accepted and not read, a plane left out (or None) counts as a plane of zeros.
+        iterations passes with tap spacing 1, 2, 4, ...; a sigma <= 0 turns its term off.
+        sigma_depth is the depth change tolerated per step of tap spacing in the scene's world
+        units, so it has no scene-independent default and is off.  tile=False sends every
+        iteration through the direct kernel (same results).  out: the (H, W, 3) float32 array to
+        write (it may be `color`: in place); default a new one.  color=None filters the
+        framebuffer of the last render(), whose size width and height then name.  Needs no
+        scene.  The call's xrt_denoise_stats are left in self.denoise_stats."""
+        bad = [n for n in guides if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        if color is not None:
+            assert color.dtype == np.float32 and color.flags.c_contiguous and color.ndim == 3 and color.shape[2] == 3
+            height, width = color.shape[:2]
+        for n in abi.DENOISE_PLANES:
+            a = guides.get(n)
+            if a is not None:
+                assert a.dtype == (np.int32 if n == "object" else np.float32) and a.flags.c_contiguous
+                assert a.shape == (height, width) + self._AOV_SHAPES[n], n
+        if out is None:
+            out = np.empty((height, width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (height, width, 3)
+        p = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing)
+        bufs = abi.XrtAovBuffers(**{n: guides[n].ctypes.data for n in abi.DENOISE_PLANES if guides.get(n) is not None})
+        st = abi.XrtDenoiseStats()
+        self._check(self._lib.xrt_denoise(self.ctx, C.byref(p), C.c_void_p(color.ctypes.data if color is not None else None),
+                                          C.byref(bufs), C.c_void_p(out.ctypes.data), C.byref(st)), "xrt_denoise")
+        self.denoise_stats = st
+        return out
+
+    def denoise_device(self, color_ptr, guide_ptrs: dict, out_ptr, width, height, after_stream=None, iterations=3,
+                       sigma_color=2.0, sigma_normal=0.5, sigma_depth=0.0, sigma_albedo=0.2, tile=True, timing=False):
+        """The filter over device memory (xrt_denoise_device): color_ptr and out_ptr are device
+        pointers to H*W*3 float32 (they may be equal; color_ptr 0 = the last render's
+        framebuffer), guide_ptrs maps plane names to device pointers laid out as
+        render_aov_device writes them.  after_stream as for render_aov_device.  The settings
+        are denoise()'s.  Returns the xrt_denoise_stats when out_ptr is complete."""
+        bad = [n for n in guide_ptrs if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        p = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing)
+        bufs = abi.XrtAovBuffers(**{n: int(guide_ptrs[n]) for n in abi.DENOISE_PLANES if guide_ptrs.get(n)})
+        st = abi.XrtDenoiseStats()
+        self._check(self._lib.xrt_denoise_device(self.ctx, C.byref(p), C.c_void_p(color_ptr or None), C.byref(bufs),
+                                                 C.c_void_p(out_ptr or None), C.c_void_p(after_stream or None),
+                                                 C.byref(st)), "xrt_denoise_device")
+        self.denoise_stats = st
+        return st
+
     def query(self, scene: SceneBundle, rays: np.ndarray, tmax=None, occluded: bool = False):
         """Scene::intersect (or, with occluded=True, Scene::occluded(ray, tmax)) for rays
         (n, 6) = origin, direction, on the GPU with the render's trace kernels (xrt_query).
