@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import aov_restatement as ar
+import multi_stats
 import pyoracle
 import whitted_bvh_scenes as wb
 from xraytracer_amd import abi
@@ -97,6 +98,27 @@ def test_multi_device_context():
     check_case("example", devices=[0, 0])
     check_case("example_shard", devices=[0, 0])
     check_case("bvh_glass", devices=[0, 0])
+
+
+def test_multi_device_stats_are_the_devices_sums():
+    """xrt_stats of a two-device guide pass against its two row shards on one device: every
+    counter of the structure the sum, the schedule's description device 0's (multi_stats)"""
+    from xraytracer_amd import scenes
+
+    s = scenes.cornell(32, 24)
+    one, two = HipRenderer(2), HipRenderer(2, devices=[0, 0])
+    try:
+        parts = []
+        for i in range(2):
+            one.render_aov(s, 32, 24, shard_index=i, shard_count=2)
+            parts.append(multi_stats.counters(one.stats))
+        assert parts[0]["samples"] == parts[1]["samples"] == 32 * 12 * 2
+        assert parts[0]["schedule"] == abi.XRT_SCHED_AOV
+        two.render_aov(s, 32, 24)
+        assert multi_stats.counters(two.stats) == multi_stats.combined(parts)
+    finally:
+        one.close()
+        two.close()
 
 
 # 6. plane subsets: supplied planes equal the full call's, nothing else is written

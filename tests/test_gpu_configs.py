@@ -32,7 +32,7 @@ def compare(img, ref):
 
 
 def partitions(n_slots, merged=False):
-    """The library's live-list partition count for a shard of n_slots (xrt_api.cpp): the merged
+    """The library's live-list partition count for a shard of n_slots (api_render.cpp): the merged
     schedule takes >= 2048 slots per partition (at most 256), the others >= 512 (at most 1024)."""
     max_parts, min_slots = (256, 2048) if merged else (1024, 512)
     n = min(max_parts, max(1, n_slots // min_slots))

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import multi_stats
 import pyoracle
 from xraytracer_amd import abi, scenes
 from xraytracer_amd.renderer import HipRenderer
@@ -66,6 +67,86 @@ def test_multi_device_output_accumulate_and_media():
     assert np.array_equal(m.render(v, 40, 30), ref)
     assert m.stats.draws == st["draws"]
     m.close()
+
+
+@pytest.mark.parametrize("integrator", ["direct", "whitted", "gi"])
+def test_multi_stats_are_the_devices_sums(single, integrator):
+    """xrt_stats of a two-device render against the two row shards rendered one by one on a
+    single device: every counter of the structure (multi_stats reads them from abi.XrtStats)
+    is the sum, `iterations` the maximum, the schedule's description device 0's.  Direct and
+    Whitted are one launch per shard, so every field is compared; GI's loop length follows
+    its polls' timing, so its launch counts are left out there and only there."""
+    skip = multi_stats.LOOP_LENGTH if integrator == "gi" else ()
+    s = scenes.cornell(32, 24)
+    single.spp = 2
+    parts, rows = [], []
+    for i in range(2):
+        rows.append(single.render(s, 32, 24, integrator=integrator, shard_index=i, shard_count=2))
+        parts.append(multi_stats.counters(single.stats, skip))
+    assert parts[0]["samples"] == parts[1]["samples"] == 32 * 12 * 2
+    m = HipRenderer(2, devices=[0, 0])
+    try:
+        img = m.render(s, 32, 24, integrator=integrator)
+        got = multi_stats.counters(m.stats, skip)
+    finally:
+        m.close()
+    assert got == multi_stats.combined(parts)
+    assert np.array_equal(img, rows[0] + rows[1])   # each shard leaves the other's rows zero
+
+
+def test_multi_device_that_owns_no_rows(single):
+    """8 x 2 pixels over three devices: the third owns no row (its shard is empty and the
+    gather skips it), and of the caller's shard 1 of 2 only the first device owns one."""
+    s = scenes.cornell(8, 2)
+    single.spp = 2
+    m = HipRenderer(2, devices=[0, 0, 0])
+    try:
+        assert np.array_equal(m.render(s, 8, 2), single.render(s, 8, 2))
+        assert m.stats.samples == 8 * 2 * 2
+        want = single.render(s, 8, 2, shard_index=1, shard_count=2)
+        assert want[1].any() and not want[0].any()
+        assert np.array_equal(m.render(s, 8, 2, shard_index=1, shard_count=2), want)
+        got, ref = m.render_aov(s, 8, 2), single.render_aov(s, 8, 2)
+        assert ref["alpha"].any()
+        for k in ref:
+            assert np.array_equal(got[k].view(np.uint32), ref[k].view(np.uint32)), k
+    finally:
+        m.close()
+
+
+def _rc_and_error(r, rc):
+    return rc, abi.lib().xrt_last_error(r.ctx).decode()
+
+
+def test_multi_setter_errors_name_the_device(single):
+    """A setter that fails on a device of a multi context reports "<entry point> on device
+    <d>: " and that device's own message, with its code."""
+    import ctypes as C
+
+    lib = abi.lib()
+    m = HipRenderer(1, devices=[0, 0])
+    try:
+        # a brick table of 1 x 2 x 2 for a 9^3 grid (ceil(9 / 8) = 2 per axis)
+        md = scenes.Medium(np.ones((9, 9, 9), np.float32), (0, 0, 0), 0.1, 0.0, (1, 1, 1), (1, 1, 1)).desc()
+        table = np.zeros(4, np.int32)
+        bricks = np.zeros(512, np.float32)
+        bg = abi.XrtBrickGrid(1, 2, 2, table.ctypes.data_as(C.POINTER(C.c_int32)), 1, abi.fptr(bricks))
+        rc1, one = _rc_and_error(single, lib.xrt_set_medium_bricks(single.ctx, C.byref(md), C.byref(bg)))
+        rc2, both = _rc_and_error(m, lib.xrt_set_medium_bricks(m.ctx, C.byref(md), C.byref(bg)))
+        assert rc1 == rc2 == abi.XRT_ERR_INVALID and "brick table dimensions" in one
+        assert both == "xrt_set_medium_bricks on device 0: " + one
+        # far more area lights than the library's limit (kMaxLights, 18)
+        s = scenes.cornell(8, 8)
+        d = abi.XrtSceneDesc.from_buffer_copy(s.desc)
+        lights = (abi.XrtLight * 1000)()
+        d.n_lights, d.lights = 1000, lights
+        rc1, one = _rc_and_error(single, lib.xrt_upload_scene(single.ctx, C.byref(d)))
+        rc2, both = _rc_and_error(m, lib.xrt_upload_scene(m.ctx, C.byref(d)))
+        assert rc1 == rc2 == abi.XRT_ERR_UNSUPPORTED and one.startswith("more than ")
+        assert both == "xrt_upload_scene on device 0: " + one
+    finally:
+        m.close()
+        single._uploaded = None   # the refused upload left `single` without a scene
 
 
 def test_cpp_multi_gpu_renderer(tmp_path):

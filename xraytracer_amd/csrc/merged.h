@@ -152,7 +152,7 @@ __device__ __forceinline__ bool plane_away(v3 o, v3 d, int axis, float c) {
 
 // Mesh::rayTriangleIntersect (Src/primitive.cpp:140-168) without branches: the same float
 // operations, and the same accept/reject decisions (NaN comparisons included).  invDet is
-// the Newton reciprocal without the IEEE fallback: only scenes with det_bounded (xrt_api.cpp:
+// the Newton reciprocal without the IEEE fallback: only scenes with det_bounded (api_scene.cpp:
 // |det| < 2^120) reach this test, where a finite det is either < kEPSILON — rejected, so
 // invDet does not matter — or inside rcp_newton's exhaustively checked exact range, and a
 // NaN det gives NaN both ways.

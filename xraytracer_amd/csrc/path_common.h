@@ -596,7 +596,7 @@ __device__ __forceinline__ v3 eval_bxdf(const DObj& ob) {   // Lambert::evaluate
 
 // x / (float)width, x / (float)height, x / aspect — the renderer's constant divisors.  Where
 // the host proved Markstein's correction with its RN(1/c) equal to IEEE division for every
-// mantissa of x (KParams::cdiv, xrt_api.cpp cdiv_exact), div_const's three operations
+// mantissa of x (KParams::cdiv, api_render.cpp cdiv_exact), div_const's three operations
 // replace the IEEE sequence; otherwise the IEEE division.  The flag is uniform: no
 // divergence.
 __device__ __forceinline__ float div_w(const KParams& P, float x) {

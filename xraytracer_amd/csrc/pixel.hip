@@ -264,7 +264,7 @@ constexpr bool pix_defer(int scn, int integ) {
 }
 constexpr uint32_t kPixPend = 192;   // pending samples of three windows (codes)
 // the 624-word stream buffer holds three windows' items and the generation lookahead only for
-// NL <= 18 (above), and the plain window's own words bound NL further; xrt_api.cpp refuses
+// NL <= 18 (above), and the plain window's own words bound NL further; api_scene.cpp refuses
 // scenes with more than kMaxLights lights
 static_assert(kMaxLights <= 18, "k_pixel's stream window assumes at most 18 area lights");
 constexpr uint32_t kPixWaveDeferLds = kPixWaveLds + 3 * kPixSumStride * 4 + 3 * 64 * 4 + kPixPend;

@@ -1,5 +1,5 @@
 // wavefront.h — device data layout of the MI355X wavefront path tracer, shared by the
-// kernels (wavefront.hip) and the host orchestration (xrt_api.cpp).
+// kernels (wavefront.hip) and the host orchestration (api_*.cpp).
 //
 // HBM layout (DESIGN.md §Data layout):
 //   scene  : triangles as 3 float4 per triangle {(v0, obj), (e1 = v1-v0, occluder), (e2 = v2-v0, 0)}
@@ -221,7 +221,7 @@ struct KParams {
     float sph_pad;            // the sphere BVH's box margin (1e-4 scene diagonal + 1e-4)
     const f4* sblk;           // per 64 ssph entries: a ball (center, radius) holding each member's ball of radius |r| + sph_pad
     int n_segs, n_lights, n_tris, n_sph, n_box, scene_kind, n_objs, small_tri;
-    int det_bounded;   // every triangle has |e1| |e2| < 2^120 (ray_tri_nb's Newton reciprocal, xrt_api.cpp)
+    int det_bounded;   // every triangle has |e1| |e2| < 2^120 (ray_tri_nb's Newton reciprocal, api_scene.cpp)
     DMedium medium;
     // ---- camera (row-major c2w) + PinholeCamera scale / aspect
     float c2w[16];
