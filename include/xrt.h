@@ -419,6 +419,66 @@ int  xrt_denoise(xrt_ctx* ctx, const xrt_denoise_params* p, const float* color, 
 int  xrt_denoise_device(xrt_ctx* ctx, const xrt_denoise_params* p, const float* d_color,
                         const xrt_aov_buffers* d_guides, float* d_out, void* hip_stream, xrt_denoise_stats* st);
 
+/* ---- denoiser, variance-guided: the spatial filter of SVGF ---------------------------- */
+/* Schied et al. 2017, section 4.3, without its temporal part: the a-trous filter above with the
+ * absolute colour stop replaced by a luminance difference measured in standard deviations of the
+ * centre pixel's own noise, and the variance filtered along with the colour, so every pass sees
+ * how much noise the passes before it left.  The luminance factor is not tightened per pass (the
+ * shrinking variance does that), so sigma_luminance is independent of the radiance scale and of
+ * the iteration count.  color, the guide planes, out, their NULL rules, ordering on hip_stream,
+ * the multi-device rule and xrt_denoise_stats are xrt_denoise's.  In addition
+ *   variance     [H][W]  the variance of the pixel's luminance: finite and >= 0.  NULL: the
+ *                        library estimates it from the frame (below)
+ *   out_variance [H][W]  optional (NULL: not wanted): the variance left after the last pass
+ * out == color and out_variance == variance are allowed; any other overlap is unspecified.
+ * The arithmetic is IEEE float32, one rounding per operation, no fused multiply-add; expf is
+ * glibc's, sqrtf and / are correctly rounded:
+ *   lum(c) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b
+ *   the estimate (variance == NULL only), r = variance_radius, for pixel p:
+ *     n = m1 = m2 = +0
+ *     for dy = -r .. r (outer), dx = -r .. r (inner), q = p + (dx, dy), q inside the image and
+ *     object[q] == object[p]:
+ *       n = n + 1.0f;  m1 = m1 + lum(c[q]);  m2 = m2 + lum(c[q]) lum(c[q])
+ *     mean = m1 / n;  v = m2 / n - mean mean;  var[p] = v > 0 ? v : +0
+ *   (the centre tap always counts, so n >= 1: a spatial variance of the pixel's own object)
+ *   inv_x = sigma_x > 0 ? 1.0f / (sigma_x * sigma_x) : +0.0f      (x = normal, depth, albedo)
+ *   iteration i = 0 .. iterations - 1, tap spacing s = 1 << i:
+ *     kz = inv_depth * (1.0f / (float)(1u << 2 i));  kn = inv_normal;  ka = inv_albedo
+ *     for pixel p, with c and var the iteration's input (the caller's or the estimate, then the
+ *     previous output):
+ *       vs = gs = +0
+ *       for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = p + (dx, dy), q inside the image:
+ *         gw = g[dy + 1] g[dx + 1],  g = {1/4, 1/2, 1/4};  vs = vs + var[q] gw;  gs = gs + gw
+ *       vg = vs / gs
+ *       kl = sigma_luminance > 0 ? 1.0f / (sigma_luminance * sqrtf(vg) + 1e-8f) : +0.0f
+ *       acc = (+0, +0, +0); vacc = +0; ws = +0
+ *       for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = p + s (dx, dy), q inside the image:
+ *         dl = fabsf(lum(c[p]) - lum(c[q]));  d2n, d2z, d2a as for xrt_denoise
+ *         e = ((dl kl + d2n kn) + d2z kz) + d2a ka
+ *         w = expf(-e) * (h[dy + 2] h[dx + 2]);  if object[p] != object[q]: w = +0
+ *         acc.ch = acc.ch + c[q].ch w;  vacc = vacc + var[q] (w w);  ws = ws + w
+ *       out[p].ch = acc.ch / ws;  var'[p] = vacc / (ws ws)
+ * The centre tap gives ws >= 9/64 for finite input.  With sigma_luminance <= 0 the colour is
+ * xrt_denoise's with sigma_color = 0, bit for bit.
+ * XRT_ERR_INVALID and XRT_ERR_STATE as for xrt_denoise, and XRT_ERR_INVALID for a variance_radius
+ * outside 1 .. XRT_DENOISE_VAR_MAX_RADIUS while variance is NULL.  xrt_denoise_stats.launches: the
+ * prepass, the estimate when it ran, and one per iteration. */
+#define XRT_DENOISE_VAR_MAX_RADIUS 3
+#define XRT_DENOISE_VAR_TILED_ITERATIONS 2   /* the first n iterations (steps 1, 2) take the LDS-tiled kernel */
+typedef struct {
+    uint32_t width, height, iterations;        /* iterations: 1 .. XRT_DENOISE_MAX_ITERATIONS        */
+    float sigma_luminance, sigma_normal, sigma_depth, sigma_albedo;   /* <= 0: the term is off */
+    uint32_t variance_radius;  /* 1 .. 3: the estimate's window, read only when `variance` is NULL  */
+    uint32_t flags;            /* XRT_DENOISE_TIMING, XRT_DENOISE_NO_TILE                           */
+} xrt_denoise_var_params;
+/* caller-owned HOST memory; blocks until done */
+int  xrt_denoise_var(xrt_ctx* ctx, const xrt_denoise_var_params* p, const float* color, const float* variance,
+                     const xrt_aov_buffers* guides, float* out, float* out_variance, xrt_denoise_stats* st);
+/* DEVICE pointers on this context's GPU (devices[0]); ordering as xrt_denoise_device */
+int  xrt_denoise_var_device(xrt_ctx* ctx, const xrt_denoise_var_params* p, const float* d_color,
+                            const float* d_variance, const xrt_aov_buffers* d_guides, float* d_out,
+                            float* d_out_variance, void* hip_stream, xrt_denoise_stats* st);
+
 /* ---- ray queries: Scene::intersect / Scene::occluded (Src/scene.cpp:190-211) ---------- */
 /* One IntersectInfo (Src/ray.h:23-39) as Scene::intersect leaves a fresh one. */
 typedef struct {

@@ -52,6 +52,17 @@ struct DenoiseSettings {
     bool tile = true, timing = false;
 };
 
+// The variance-guided filter's settings (xrt.h, xrt_denoise_var): the colour stop is a luminance
+// difference in standard deviations of the pixel's own noise, sigma_luminance of them, so it needs
+// no tuning to the radiance scale or the iteration count.  The variance is estimated from the frame
+// over a window of (2 variance_radius + 1)^2 pixels of the same object (1 .. 3).
+struct DenoiseVarSettings {
+    uint32_t iterations = 4;
+    float sigma_luminance = 4.0f, sigma_normal = 0.5f, sigma_depth = 0.0f, sigma_albedo = 0.2f;
+    uint32_t variance_radius = 3;
+    bool tile = true, timing = false;
+};
+
 struct xrt_ctx;
 class HipRenderer : public Renderer {
 public:
@@ -70,6 +81,11 @@ public:
     // passed as NULL: planes of zeros; alpha is not read).  Needs no scene; creates the context
     // if no call has yet.  Errors as render() reports them.
     void denoise(Image& image, const GuideImages& guides, const DenoiseSettings& settings = {}) const;
+    // As denoise(), through the variance-guided filter with the variance estimated from `image`;
+    // variance_out, when given, is resized to width * height and receives the variance left after
+    // the last pass.
+    void denoiseVar(Image& image, const GuideImages& guides, const DenoiseVarSettings& settings = {},
+                    std::vector<float>* variance_out = nullptr) const;
     int lastStatus() const { return m_status; }
     const std::string& lastError() const { return m_error; }
     const xrt_stats& lastStats() const { return m_stats; }

@@ -43,6 +43,8 @@ AOV_PLANES = ("albedo", "normal", "depth", "alpha", "object")   # xrt_aov_buffer
 XRT_DENOISE_MAX_ITERATIONS = 6
 XRT_DENOISE_TILED_ITERATIONS = 2   # include/xrt.h: the first n iterations take the LDS-tiled kernel
 XRT_DENOISE_TIMING, XRT_DENOISE_NO_TILE = 1, 2
+XRT_DENOISE_VAR_MAX_RADIUS = 3
+XRT_DENOISE_VAR_TILED_ITERATIONS = 2   # include/xrt.h: the first n iterations of xrt_denoise_var take the LDS-tiled kernel
 DENOISE_PLANES = ("albedo", "normal", "depth", "object")   # the guide planes xrt_denoise reads
 SCHEDULE_NAMES = ("wavefront", "step", "step_tri", "step_merged", "step_bvh", "pixel", "whitted", "whitted_bvh",
                   "aov")
@@ -141,6 +143,12 @@ class XrtDenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
 
 
+class XrtDenoiseVarParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("variance_radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class XrtDenoiseStats(C.Structure):
     _fields_ = [("wall_ms", C.c_double), ("kernel_ms", C.c_double), ("launches", C.c_uint32),
                 ("tiled_iterations", C.c_uint32), ("direct_iterations", C.c_uint32), ("reserved", C.c_uint32)]
@@ -179,6 +187,11 @@ SIGNATURES = {
                               C.POINTER(XrtDenoiseStats)]),
     "xrt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(XrtDenoiseParams), C.c_void_p, C.POINTER(XrtAovBuffers),
                                      C.c_void_p, C.c_void_p, C.POINTER(XrtDenoiseStats)]),
+    "xrt_denoise_var": (C.c_int, [C.c_void_p, C.POINTER(XrtDenoiseVarParams), C.c_void_p, C.c_void_p,
+                                  C.POINTER(XrtAovBuffers), C.c_void_p, C.c_void_p, C.POINTER(XrtDenoiseStats)]),
+    "xrt_denoise_var_device": (C.c_int, [C.c_void_p, C.POINTER(XrtDenoiseVarParams), C.c_void_p, C.c_void_p,
+                                         C.POINTER(XrtAovBuffers), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(XrtDenoiseStats)]),
     "xrt_hscene_create": (C.c_void_p, []),
     "xrt_hscene_destroy": (None, [C.c_void_p]),
     "xrt_hscene_last_error": (C.c_char_p, [C.c_void_p]),

@@ -59,8 +59,8 @@ struct xrt_ctx {
     // guide buffers (xrt_render_aov): per object the albedo as uploaded (3 floats; DObj keeps
     // only albedo / PI), and the context's own planes (host output, sub-contexts of a multi render)
     xrt::DevBuf obj_albedo, aov;
-    // xrt_denoise: the per-pixel records (two colour buffers, normal, albedo: 16 B each), then for
-    // the host entry point the staged input planes and the output image
+    // xrt_denoise, xrt_denoise_var: the per-pixel records (two colour buffers, normal, albedo: 16 B
+    // each), then for the host entry points the staged input planes and the output planes
     xrt::DevBuf denoise;
 };
 

@@ -23,9 +23,6 @@
 
 namespace xrt {
 
-constexpr int kDnTileW = 32, kDnTileH = 8;   // pixels per block: a wave is two 32-pixel row pieces
-constexpr int kDnBlock = kDnTileW * kDnTileH;
-
 struct DnPix {
     f4 c, n, a;   // the three records of one pixel
 };

@@ -84,32 +84,61 @@ void HipRenderer::renderGuides(const Scene& scene, GuideImages& g) const {
     if (rc != XRT_OK) fail(rc, std::string("xrt_render_aov: ") + xrt_last_error(m_ctx));
 }
 
+// the filters' view of `g` for a w x h image: a guide plane takes part when it has a size, and then
+// it has the image's (false otherwise).  xrt_aov_buffers serves outputs elsewhere; the filters only
+// read through it.
+static bool guide_inputs(uint32_t w, uint32_t h, const GuideImages& g, xrt_aov_buffers& in) {
+    const size_t npix = (size_t)w * h;
+    const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
+    if ((na && (g.albedo.getWidth() != w || g.albedo.getHeight() != h)) ||
+        (nn && (g.normal.getWidth() != w || g.normal.getHeight() != h)) || (!g.depth.empty() && g.depth.size() != npix) ||
+        (!g.object.empty() && g.object.size() != npix))
+        return false;
+    in = xrt_aov_buffers{na ? const_cast<float*>(g.albedo.data()) : nullptr, nn ? const_cast<float*>(g.normal.data()) : nullptr,
+                         g.depth.empty() ? nullptr : const_cast<float*>(g.depth.data()), nullptr,
+                         g.object.empty() ? nullptr : const_cast<int32_t*>(g.object.data())};
+    return true;
+}
+
 void HipRenderer::denoise(Image& image, const GuideImages& g, const DenoiseSettings& s) const {
     auto fail = [&](int rc, const std::string& msg) {
         m_status = rc;
         m_error = msg;
         std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
     };
-    // a guide plane takes part when it has a size, and then it has the image's
-    const uint32_t w = image.getWidth(), h = image.getHeight();
-    const size_t npix = (size_t)w * h;
-    const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
-    if ((na && (g.albedo.getWidth() != w || g.albedo.getHeight() != h)) ||
-        (nn && (g.normal.getWidth() != w || g.normal.getHeight() != h)) || (!g.depth.empty() && g.depth.size() != npix) ||
-        (!g.object.empty() && g.object.size() != npix))
+    xrt_aov_buffers in;
+    if (!guide_inputs(image.getWidth(), image.getHeight(), g, in))
         return fail(XRT_ERR_INVALID, "denoise: every sized member of GuideImages must have the image's size");
     if (context() != XRT_OK) return;
     xrt_denoise_params p;
     std::memset(&p, 0, sizeof(p));
-    p.width = w, p.height = h, p.iterations = s.iterations;
+    p.width = image.getWidth(), p.height = image.getHeight(), p.iterations = s.iterations;
     p.sigma_color = s.sigma_color, p.sigma_normal = s.sigma_normal, p.sigma_depth = s.sigma_depth, p.sigma_albedo = s.sigma_albedo;
     p.flags = (s.timing ? XRT_DENOISE_TIMING : 0u) | (s.tile ? 0u : XRT_DENOISE_NO_TILE);
-    // xrt_aov_buffers serves outputs elsewhere; the filter only reads through it
-    const xrt_aov_buffers in{na ? const_cast<float*>(g.albedo.data()) : nullptr, nn ? const_cast<float*>(g.normal.data()) : nullptr,
-                             g.depth.empty() ? nullptr : const_cast<float*>(g.depth.data()), nullptr,
-                             g.object.empty() ? nullptr : const_cast<int32_t*>(g.object.data())};
     const int rc = xrt_denoise(m_ctx, &p, image.data(), &in, image.data(), &m_denoise_stats);
     if (rc != XRT_OK) fail(rc, std::string("xrt_denoise: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::denoiseVar(Image& image, const GuideImages& g, const DenoiseVarSettings& s, std::vector<float>* variance_out) const {
+    auto fail = [&](int rc, const std::string& msg) {
+        m_status = rc;
+        m_error = msg;
+        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+    };
+    xrt_aov_buffers in;
+    if (!guide_inputs(image.getWidth(), image.getHeight(), g, in))
+        return fail(XRT_ERR_INVALID, "denoiseVar: every sized member of GuideImages must have the image's size");
+    if (context() != XRT_OK) return;
+    xrt_denoise_var_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = image.getWidth(), p.height = image.getHeight(), p.iterations = s.iterations;
+    p.sigma_luminance = s.sigma_luminance, p.sigma_normal = s.sigma_normal, p.sigma_depth = s.sigma_depth;
+    p.sigma_albedo = s.sigma_albedo, p.variance_radius = s.variance_radius;
+    p.flags = (s.timing ? XRT_DENOISE_TIMING : 0u) | (s.tile ? 0u : XRT_DENOISE_NO_TILE);
+    if (variance_out) variance_out->assign((size_t)p.width * p.height, 0.0f);
+    const int rc = xrt_denoise_var(m_ctx, &p, image.data(), nullptr, &in, image.data(), variance_out ? variance_out->data() : nullptr,
+                                   &m_denoise_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_denoise_var: ") + xrt_last_error(m_ctx));
 }
 
 void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image) const {

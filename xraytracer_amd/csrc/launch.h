@@ -111,6 +111,34 @@ hipError_t launch_denoise_pack(const float* color, const float* albedo, const fl
                                const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb, hipStream_t st);
 bool denoise_has_tiled(int step);
 hipError_t launch_denoise_iter(const DenoiseIter& I, bool tiled, hipStream_t st);
+// pixels per block of every filter kernel: a wave is two 32-pixel row pieces
+constexpr int kDnTileW = 32, kDnTileH = 8;
+constexpr int kDnBlock = kDnTileW * kDnTileH;
+// Variance-guided a-trous filter (denoise_var.hip, xrt_denoise_var).  The variance changes per pass,
+// so it travels with the colour: col = {c.rgb, var}, nrm = {n.xyz, object bits}, alb = {albedo.rgb,
+// depth}.  launch_dnv_pack gathers the caller's planes into col, nrm, alb (variance null: var = +0,
+// to be replaced by the estimate).  launch_dnv_estimate reads cin's rgb and nrm's object and writes
+// cout = {cin.rgb, the estimated variance}: cout is another buffer than cin, so no lane reads what the
+// launch writes.  launch_dnv_iter runs one iteration from cin: into the col records cout, or, when
+// out3 is set (the last iteration), into that packed float3 image and, when outv is set, that
+// variance plane.  tiled as for launch_denoise_iter, for the steps dnv_has_tiled names.
+struct DnvK {
+    float sl, kn, kz, ka;   // sigma_luminance (<= 0: off); the factors on the squared normal / depth / albedo distance
+};
+struct DnvIter {
+    const f4 *cin, *nrm, *alb;
+    f4* cout;
+    float *out3, *outv;
+    uint32_t width, height;
+    int step;
+    DnvK K;
+};
+hipError_t launch_dnv_pack(const float* color, const float* variance, const float* albedo, const float* normal,
+                           const float* depth, const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb, hipStream_t st);
+hipError_t launch_dnv_estimate(const f4* cin, const f4* nrm, f4* cout, uint32_t width, uint32_t height, int radius,
+                               hipStream_t st);
+bool dnv_has_tiled(int step);
+hipError_t launch_dnv_iter(const DnvIter& I, bool tiled, hipStream_t st);
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned

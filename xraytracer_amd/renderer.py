@@ -220,6 +220,79 @@ class HipRenderer:
         self.denoise_stats = st
         return st
 
+    @staticmethod
+    def _denoise_var_params(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
+                            variance_radius, tile, timing):
+        return abi.XrtDenoiseVarParams(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
+                                       variance_radius,
+                                       (abi.XRT_DENOISE_TIMING if timing else 0) | (0 if tile else abi.XRT_DENOISE_NO_TILE))
+
+    def denoise_var(self, color, guides: dict, variance=None, iterations=4, sigma_luminance=4.0, sigma_normal=0.5,
+                    sigma_depth=0.0, sigma_albedo=0.2, variance_radius=3, tile=True, timing=False, out=None,
+                    out_variance=None, want_variance=True, width=None, height=None):
+        """Variance-guided a-trous filter (xrt_denoise_var, SVGF's spatial filter) of the (H, W, 3)
+        float32 frame `color` over `guides` as denoise() takes them.  The colour stop is the
+        luminance difference in units of sigma_luminance standard deviations of the centre
+        pixel's noise, so it needs no tuning to the radiance scale.  variance: the (H, W) float32
+        variance of each pixel's luminance (finite, >= 0); None: estimated from the frame over
+        (2 variance_radius + 1)^2 pixels of the same object (variance_radius 1 .. 3).  out,
+        out_variance: the arrays to write (they may be `color` and `variance`: in place);
+        default new ones.  want_variance=False passes no variance output.  color=None, tile,
+        timing, width, height as for denoise().  Returns (out, out_variance), out_variance None
+        when not wanted; the call's xrt_denoise_stats are left in self.denoise_stats."""
+        bad = [n for n in guides if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        if color is not None:
+            assert color.dtype == np.float32 and color.flags.c_contiguous and color.ndim == 3 and color.shape[2] == 3
+            height, width = color.shape[:2]
+        for n in abi.DENOISE_PLANES:
+            a = guides.get(n)
+            if a is not None:
+                assert a.dtype == (np.int32 if n == "object" else np.float32) and a.flags.c_contiguous
+                assert a.shape == (height, width) + self._AOV_SHAPES[n], n
+        if variance is not None:
+            assert variance.dtype == np.float32 and variance.flags.c_contiguous and variance.shape == (height, width)
+        if out is None:
+            out = np.empty((height, width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (height, width, 3)
+        if out_variance is None and want_variance:
+            out_variance = np.empty((height, width), np.float32)
+        if out_variance is not None:
+            assert out_variance.dtype == np.float32 and out_variance.flags.c_contiguous and out_variance.shape == (height, width)
+        p = self._denoise_var_params(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
+                                     variance_radius, tile, timing)
+        bufs = abi.XrtAovBuffers(**{n: guides[n].ctypes.data for n in abi.DENOISE_PLANES if guides.get(n) is not None})
+        st = abi.XrtDenoiseStats()
+        self._check(self._lib.xrt_denoise_var(
+            self.ctx, C.byref(p), C.c_void_p(color.ctypes.data if color is not None else None),
+            C.c_void_p(variance.ctypes.data if variance is not None else None), C.byref(bufs), C.c_void_p(out.ctypes.data),
+            C.c_void_p(out_variance.ctypes.data if out_variance is not None else None), C.byref(st)), "xrt_denoise_var")
+        self.denoise_stats = st
+        return out, out_variance
+
+    def denoise_var_device(self, color_ptr, guide_ptrs: dict, out_ptr, width, height, variance_ptr=0, out_variance_ptr=0,
+                           after_stream=None, iterations=4, sigma_luminance=4.0, sigma_normal=0.5, sigma_depth=0.0,
+                           sigma_albedo=0.2, variance_radius=3, tile=True, timing=False):
+        """The variance-guided filter over device memory (xrt_denoise_var_device): color_ptr, out_ptr
+        and guide_ptrs as for denoise_device; variance_ptr and out_variance_ptr are device pointers
+        to H*W float32 (they may be equal; variance_ptr 0 = estimate it, out_variance_ptr 0 = not
+        wanted).  The settings are denoise_var()'s.  Returns the xrt_denoise_stats when the outputs
+        are complete."""
+        bad = [n for n in guide_ptrs if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        p = self._denoise_var_params(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
+                                     variance_radius, tile, timing)
+        bufs = abi.XrtAovBuffers(**{n: int(guide_ptrs[n]) for n in abi.DENOISE_PLANES if guide_ptrs.get(n)})
+        st = abi.XrtDenoiseStats()
+        self._check(self._lib.xrt_denoise_var_device(
+            self.ctx, C.byref(p), C.c_void_p(color_ptr or None), C.c_void_p(variance_ptr or None), C.byref(bufs),
+            C.c_void_p(out_ptr or None), C.c_void_p(out_variance_ptr or None), C.c_void_p(after_stream or None), C.byref(st)),
+            "xrt_denoise_var_device")
+        self.denoise_stats = st
+        return st
+
     def query(self, scene: SceneBundle, rays: np.ndarray, tmax=None, occluded: bool = False):
         """Scene::intersect (or, with occluded=True, Scene::occluded(ray, tmax)) for rays
         (n, 6) = origin, direction, on the GPU with the render's trace kernels (xrt_query).
