@@ -94,6 +94,10 @@ public:
 private:
     int context() const;                     // creates the context on first use; XRT_OK or fails with m_error set
     int prepare(const Scene& scene) const;   // context, scene, delta lights, camera; XRT_OK or fails with m_error set
+    void fail(int rc, const std::string& msg) const;   // m_status, m_error and a line on stderr
+    // the start of denoise() / denoiseVar() (`who`): the guide planes of `guides` that have a size, as
+    // the filters read them, and the context; false after fail()
+    bool filterInputs(const char* who, const Image& image, const GuideImages& guides, xrt_aov_buffers& in) const;
     const uint32_t n_samples;
     int m_device;
     std::vector<int> m_devices;   // empty: one GPU (m_device)

@@ -1,4 +1,4 @@
-"""The variance-guided a-trous filter on the GPU (xrt_denoise_var, denoise_var.hip) against the
+"""The variance-guided a-trous filter on the GPU (xrt_denoise_var, denoise.hip) against the
 restatement (tests/denoise_var_restatement.py): every frame and the variance left bit for bit, under
 the default path and under XRT_DENOISE_NO_TILE.  The cases and the situations they are chosen for
 are in tests/denoise_var_restatement.py and checked without a GPU in
@@ -266,7 +266,29 @@ def test_timing_flag(r):
     assert r.denoise_stats.kernel_ms == 0 and r.denoise_stats.wall_ms > 0
 
 
-# 11. end to end: a GPU GI render, its guide buffers and the filter, against the restatement applied to
+# 11. the two filters share the context's records and staging: neither sees what the other left.  The
+#     larger frame goes first, so each later call runs in a buffer that still holds the other
+#     filter's larger records.
+def test_filters_alternate_in_one_context():
+    plain_color, plain_g = dr.inputs("synthetic_3")   # 37 x 29
+    plain_kw = dr.CASES["synthetic_3"][3]
+    hr = HipRenderer(1)
+    try:
+        for tile in (True, False):
+            plain = []
+            for name in ("130x70", "supplied"):
+                color, g, variance = dv.inputs(name)
+                got, var = hr.denoise_var(color, g, variance, tile=tile, **dv.CASES[name][4])
+                assert_same(got, dv.reference(name)[0])
+                assert_same(var, dv.reference(name)[1])
+                plain.append(hr.denoise(plain_color, plain_g, tile=tile, **plain_kw))
+                assert_same(plain[-1], dr.reference("synthetic_3")[0])
+            assert_same(plain[0], plain[1])
+    finally:
+        hr.close()
+
+
+# 12. end to end: a GPU GI render, its guide buffers and the filter, against the restatement applied to
 #     those same GPU outputs
 def test_render_guides_denoise_var():
     w, h, spp = 64, 48, 16

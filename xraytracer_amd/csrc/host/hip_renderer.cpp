@@ -58,12 +58,13 @@ int HipRenderer::prepare(const Scene& scene) const {
     return XRT_OK;
 }
 
+void HipRenderer::fail(int rc, const std::string& msg) const {
+    m_status = rc;
+    m_error = msg;
+    std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+}
+
 void HipRenderer::renderGuides(const Scene& scene, GuideImages& g) const {
-    auto fail = [&](int rc, const std::string& msg) {
-        m_status = rc;
-        m_error = msg;
-        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
-    };
     // a member takes part when it has a size, and then it has the frame's
     const size_t npix = (size_t)g.width * g.height;
     const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
@@ -84,32 +85,27 @@ void HipRenderer::renderGuides(const Scene& scene, GuideImages& g) const {
     if (rc != XRT_OK) fail(rc, std::string("xrt_render_aov: ") + xrt_last_error(m_ctx));
 }
 
-// the filters' view of `g` for a w x h image: a guide plane takes part when it has a size, and then
-// it has the image's (false otherwise).  xrt_aov_buffers serves outputs elsewhere; the filters only
-// read through it.
-static bool guide_inputs(uint32_t w, uint32_t h, const GuideImages& g, xrt_aov_buffers& in) {
+// A guide plane takes part when it has a size, and then it has the image's.  xrt_aov_buffers serves
+// outputs elsewhere; the filters only read through it.
+bool HipRenderer::filterInputs(const char* who, const Image& image, const GuideImages& g, xrt_aov_buffers& in) const {
+    const uint32_t w = image.getWidth(), h = image.getHeight();
     const size_t npix = (size_t)w * h;
     const size_t na = (size_t)g.albedo.getWidth() * g.albedo.getHeight(), nn = (size_t)g.normal.getWidth() * g.normal.getHeight();
     if ((na && (g.albedo.getWidth() != w || g.albedo.getHeight() != h)) ||
         (nn && (g.normal.getWidth() != w || g.normal.getHeight() != h)) || (!g.depth.empty() && g.depth.size() != npix) ||
-        (!g.object.empty() && g.object.size() != npix))
+        (!g.object.empty() && g.object.size() != npix)) {
+        fail(XRT_ERR_INVALID, std::string(who) + ": every sized member of GuideImages must have the image's size");
         return false;
+    }
     in = xrt_aov_buffers{na ? const_cast<float*>(g.albedo.data()) : nullptr, nn ? const_cast<float*>(g.normal.data()) : nullptr,
                          g.depth.empty() ? nullptr : const_cast<float*>(g.depth.data()), nullptr,
                          g.object.empty() ? nullptr : const_cast<int32_t*>(g.object.data())};
-    return true;
+    return context() == XRT_OK;
 }
 
 void HipRenderer::denoise(Image& image, const GuideImages& g, const DenoiseSettings& s) const {
-    auto fail = [&](int rc, const std::string& msg) {
-        m_status = rc;
-        m_error = msg;
-        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
-    };
     xrt_aov_buffers in;
-    if (!guide_inputs(image.getWidth(), image.getHeight(), g, in))
-        return fail(XRT_ERR_INVALID, "denoise: every sized member of GuideImages must have the image's size");
-    if (context() != XRT_OK) return;
+    if (!filterInputs("denoise", image, g, in)) return;
     xrt_denoise_params p;
     std::memset(&p, 0, sizeof(p));
     p.width = image.getWidth(), p.height = image.getHeight(), p.iterations = s.iterations;
@@ -120,15 +116,8 @@ void HipRenderer::denoise(Image& image, const GuideImages& g, const DenoiseSetti
 }
 
 void HipRenderer::denoiseVar(Image& image, const GuideImages& g, const DenoiseVarSettings& s, std::vector<float>* variance_out) const {
-    auto fail = [&](int rc, const std::string& msg) {
-        m_status = rc;
-        m_error = msg;
-        std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
-    };
     xrt_aov_buffers in;
-    if (!guide_inputs(image.getWidth(), image.getHeight(), g, in))
-        return fail(XRT_ERR_INVALID, "denoiseVar: every sized member of GuideImages must have the image's size");
-    if (context() != XRT_OK) return;
+    if (!filterInputs("denoiseVar", image, g, in)) return;
     xrt_denoise_var_params p;
     std::memset(&p, 0, sizeof(p));
     p.width = image.getWidth(), p.height = image.getHeight(), p.iterations = s.iterations;

@@ -89,56 +89,42 @@ struct AovOut {
 };
 int aov_kernel(const KParams& P);
 hipError_t launch_aov(const KParams& P, const AovOut& A, uint32_t* work, hipStream_t st);
-// Edge-avoiding a-trous filter (denoise.hip, xrt_denoise).  launch_denoise_pack gathers the
-// caller's planes (device pointers; color is required, a null guide plane packs as zeros) into
-// the per-pixel records col = {c.rgb, depth}, nrm = {n.xyz, object bits}, alb = {albedo.rgb, 0}.
-// launch_denoise_iter runs one iteration with tap spacing `step` pixels from cin: into the col
-// records cout, or, when out3 is set (the last iteration), into that packed float3 image.
-// tiled: through the LDS-tiled kernel, which exists for the steps denoise_has_tiled names; both
-// kernels give the same bits.
+// The two a-trous filters (denoise.hip): the edge-avoiding one (xrt_denoise) and the variance-guided
+// one (xrt_denoise_var), which share records, kernels and launches.  launch_denoise_pack gathers the
+// caller's planes (device pointers; color is required, a null plane packs as zeros) into the
+// per-pixel records col = {c.rgb, variance}, nrm = {n.xyz, object bits}, alb = {albedo.rgb, depth};
+// the plain filter passes no variance and carries +0 there.  launch_dnv_estimate (the variance
+// filter without a caller's variance) reads cin's rgb and nrm's object and writes cout = {cin.rgb,
+// the estimated variance}: cout is another buffer than cin, so no lane reads what the launch writes.
+// launch_denoise_iter runs one iteration of `filter` with tap spacing `step` pixels from cin: into
+// the col records cout, or, when out3 is set (the last iteration), into that packed float3 image
+// and, when outv is set (the variance filter only), that variance plane.  tiled: through the
+// LDS-tiled kernel, which exists for the steps denoise_has_tiled names; both kernels give the same
+// bits.
+enum class DenoiseFilter { Plain, Var };
 struct DenoiseK {
-    float kc, kn, kz, ka;   // the iteration's factors on the squared colour / normal / depth / albedo distance
+    // k0: the plain filter's factor on the squared colour distance; the variance filter's
+    // sigma_luminance (<= 0: off).  The factors on the squared normal / depth / albedo distance.
+    float k0, kn, kz, ka;
 };
 struct DenoiseIter {
-    const f4 *cin, *nrm, *alb;
-    f4* cout;
-    float* out3;
-    uint32_t width, height;
-    int step;
-    DenoiseK K;
-};
-hipError_t launch_denoise_pack(const float* color, const float* albedo, const float* normal, const float* depth,
-                               const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb, hipStream_t st);
-bool denoise_has_tiled(int step);
-hipError_t launch_denoise_iter(const DenoiseIter& I, bool tiled, hipStream_t st);
-// pixels per block of every filter kernel: a wave is two 32-pixel row pieces
-constexpr int kDnTileW = 32, kDnTileH = 8;
-constexpr int kDnBlock = kDnTileW * kDnTileH;
-// Variance-guided a-trous filter (denoise_var.hip, xrt_denoise_var).  The variance changes per pass,
-// so it travels with the colour: col = {c.rgb, var}, nrm = {n.xyz, object bits}, alb = {albedo.rgb,
-// depth}.  launch_dnv_pack gathers the caller's planes into col, nrm, alb (variance null: var = +0,
-// to be replaced by the estimate).  launch_dnv_estimate reads cin's rgb and nrm's object and writes
-// cout = {cin.rgb, the estimated variance}: cout is another buffer than cin, so no lane reads what the
-// launch writes.  launch_dnv_iter runs one iteration from cin: into the col records cout, or, when
-// out3 is set (the last iteration), into that packed float3 image and, when outv is set, that
-// variance plane.  tiled as for launch_denoise_iter, for the steps dnv_has_tiled names.
-struct DnvK {
-    float sl, kn, kz, ka;   // sigma_luminance (<= 0: off); the factors on the squared normal / depth / albedo distance
-};
-struct DnvIter {
     const f4 *cin, *nrm, *alb;
     f4* cout;
     float *out3, *outv;
     uint32_t width, height;
     int step;
-    DnvK K;
+    DenoiseK K;
 };
-hipError_t launch_dnv_pack(const float* color, const float* variance, const float* albedo, const float* normal,
-                           const float* depth, const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb, hipStream_t st);
+hipError_t launch_denoise_pack(const float* color, const float* variance, const float* albedo, const float* normal,
+                               const float* depth, const int32_t* object, size_t npix, f4* col, f4* nrm, f4* alb,
+                               hipStream_t st);
 hipError_t launch_dnv_estimate(const f4* cin, const f4* nrm, f4* cout, uint32_t width, uint32_t height, int radius,
                                hipStream_t st);
-bool dnv_has_tiled(int step);
-hipError_t launch_dnv_iter(const DnvIter& I, bool tiled, hipStream_t st);
+bool denoise_has_tiled(int step);
+hipError_t launch_denoise_iter(DenoiseFilter filter, const DenoiseIter& I, bool tiled, hipStream_t st);
+// pixels per block of every filter kernel: a wave is two 32-pixel row pieces
+constexpr int kDnTileW = 32, kDnTileH = 8;
+constexpr int kDnBlock = kDnTileW * kDnTileH;
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 // up to `visits` path segments per live slot; appends survivors to out (partitioned

@@ -162,6 +162,30 @@ class HipRenderer:
         self.stats = st
         return st
 
+    def _filter_inputs(self, color, guides, width, height):
+        """The filters' host inputs checked: (width, height, XrtAovBuffers over `guides`); the
+        size is `color`'s when there is one."""
+        bad = [n for n in guides if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        if color is not None:
+            assert color.dtype == np.float32 and color.flags.c_contiguous and color.ndim == 3 and color.shape[2] == 3
+            height, width = color.shape[:2]
+        for n in abi.DENOISE_PLANES:
+            a = guides.get(n)
+            if a is not None:
+                assert a.dtype == (np.int32 if n == "object" else np.float32) and a.flags.c_contiguous
+                assert a.shape == (height, width) + self._AOV_SHAPES[n], n
+        return width, height, abi.XrtAovBuffers(**{n: guides[n].ctypes.data for n in abi.DENOISE_PLANES
+                                                   if guides.get(n) is not None})
+
+    def _filter_inputs_device(self, guide_ptrs):
+        """The XrtAovBuffers over a dict of device pointers, its names checked."""
+        bad = [n for n in guide_ptrs if n not in self._AOV_SHAPES]
+        if bad:
+            raise ValueError(f"unknown guide planes {bad}")
+        return abi.XrtAovBuffers(**{n: int(guide_ptrs[n]) for n in abi.DENOISE_PLANES if guide_ptrs.get(n)})
+
     @staticmethod
     def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing):
         return abi.XrtDenoiseParams(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo,
@@ -179,22 +203,11 @@ class HipRenderer:
         write (it may be `color`: in place); default a new one.  color=None filters the
         framebuffer of the last render(), whose size width and height then name.  Needs no
         scene.  The call's xrt_denoise_stats are left in self.denoise_stats."""
-        bad = [n for n in guides if n not in self._AOV_SHAPES]
-        if bad:
-            raise ValueError(f"unknown guide planes {bad}")
-        if color is not None:
-            assert color.dtype == np.float32 and color.flags.c_contiguous and color.ndim == 3 and color.shape[2] == 3
-            height, width = color.shape[:2]
-        for n in abi.DENOISE_PLANES:
-            a = guides.get(n)
-            if a is not None:
-                assert a.dtype == (np.int32 if n == "object" else np.float32) and a.flags.c_contiguous
-                assert a.shape == (height, width) + self._AOV_SHAPES[n], n
+        width, height, bufs = self._filter_inputs(color, guides, width, height)
         if out is None:
             out = np.empty((height, width, 3), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (height, width, 3)
         p = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing)
-        bufs = abi.XrtAovBuffers(**{n: guides[n].ctypes.data for n in abi.DENOISE_PLANES if guides.get(n) is not None})
         st = abi.XrtDenoiseStats()
         self._check(self._lib.xrt_denoise(self.ctx, C.byref(p), C.c_void_p(color.ctypes.data if color is not None else None),
                                           C.byref(bufs), C.c_void_p(out.ctypes.data), C.byref(st)), "xrt_denoise")
@@ -208,11 +221,8 @@ class HipRenderer:
         framebuffer), guide_ptrs maps plane names to device pointers laid out as
         render_aov_device writes them.  after_stream as for render_aov_device.  The settings
         are denoise()'s.  Returns the xrt_denoise_stats when out_ptr is complete."""
-        bad = [n for n in guide_ptrs if n not in self._AOV_SHAPES]
-        if bad:
-            raise ValueError(f"unknown guide planes {bad}")
+        bufs = self._filter_inputs_device(guide_ptrs)
         p = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, tile, timing)
-        bufs = abi.XrtAovBuffers(**{n: int(guide_ptrs[n]) for n in abi.DENOISE_PLANES if guide_ptrs.get(n)})
         st = abi.XrtDenoiseStats()
         self._check(self._lib.xrt_denoise_device(self.ctx, C.byref(p), C.c_void_p(color_ptr or None), C.byref(bufs),
                                                  C.c_void_p(out_ptr or None), C.c_void_p(after_stream or None),
@@ -240,17 +250,7 @@ class HipRenderer:
         default new ones.  want_variance=False passes no variance output.  color=None, tile,
         timing, width, height as for denoise().  Returns (out, out_variance), out_variance None
         when not wanted; the call's xrt_denoise_stats are left in self.denoise_stats."""
-        bad = [n for n in guides if n not in self._AOV_SHAPES]
-        if bad:
-            raise ValueError(f"unknown guide planes {bad}")
-        if color is not None:
-            assert color.dtype == np.float32 and color.flags.c_contiguous and color.ndim == 3 and color.shape[2] == 3
-            height, width = color.shape[:2]
-        for n in abi.DENOISE_PLANES:
-            a = guides.get(n)
-            if a is not None:
-                assert a.dtype == (np.int32 if n == "object" else np.float32) and a.flags.c_contiguous
-                assert a.shape == (height, width) + self._AOV_SHAPES[n], n
+        width, height, bufs = self._filter_inputs(color, guides, width, height)
         if variance is not None:
             assert variance.dtype == np.float32 and variance.flags.c_contiguous and variance.shape == (height, width)
         if out is None:
@@ -262,7 +262,6 @@ class HipRenderer:
             assert out_variance.dtype == np.float32 and out_variance.flags.c_contiguous and out_variance.shape == (height, width)
         p = self._denoise_var_params(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
                                      variance_radius, tile, timing)
-        bufs = abi.XrtAovBuffers(**{n: guides[n].ctypes.data for n in abi.DENOISE_PLANES if guides.get(n) is not None})
         st = abi.XrtDenoiseStats()
         self._check(self._lib.xrt_denoise_var(
             self.ctx, C.byref(p), C.c_void_p(color.ctypes.data if color is not None else None),
@@ -279,12 +278,9 @@ class HipRenderer:
         to H*W float32 (they may be equal; variance_ptr 0 = estimate it, out_variance_ptr 0 = not
         wanted).  The settings are denoise_var()'s.  Returns the xrt_denoise_stats when the outputs
         are complete."""
-        bad = [n for n in guide_ptrs if n not in self._AOV_SHAPES]
-        if bad:
-            raise ValueError(f"unknown guide planes {bad}")
+        bufs = self._filter_inputs_device(guide_ptrs)
         p = self._denoise_var_params(width, height, iterations, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo,
                                      variance_radius, tile, timing)
-        bufs = abi.XrtAovBuffers(**{n: int(guide_ptrs[n]) for n in abi.DENOISE_PLANES if guide_ptrs.get(n)})
         st = abi.XrtDenoiseStats()
         self._check(self._lib.xrt_denoise_var_device(
             self.ctx, C.byref(p), C.c_void_p(color_ptr or None), C.c_void_p(variance_ptr or None), C.byref(bufs),
