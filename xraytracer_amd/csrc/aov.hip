@@ -99,10 +99,10 @@ __device__ __forceinline__ void aov_pixels(const KParams& P, const AovOut& A, co
                 uint32_t ci = (o % kMT) + 2u * (uint32_t)lane;
                 if (ci >= kMT) ci -= kMT;
                 LdsRng rng{st, ci};
-                const float cu = div_w(P, (float)(int)col + rng.next());
-                const float cv = div_h(P, (float)(int)row + rng.next());
+                const float jx = rng.next();
+                const float jy = rng.next();
                 v3 ro, rd;
-                camera_ray(P, cu, cv, ro, rd);
+                jitter_ray(P, col, row, jx, jy, ro, rd);
                 HitRec h;
                 T.closest(ro, rd, h);
                 Surf S;

@@ -1,5 +1,5 @@
 // bvh.h — host-side bounding volume hierarchy over a scene's primitives (triangles of
-// large triangle scenes, C4), consumed by k_trace_bvh (wavefront.hip).
+// large triangle scenes, C4), consumed by k_trace_bvh (trace.hip).
 //
 // The reference scans every primitive (Scene::intersect, Src/scene.cpp:190-200); the
 // hierarchy only decides which primitives a ray needs to be tested against, and the

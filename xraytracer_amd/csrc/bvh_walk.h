@@ -1,5 +1,5 @@
 // bvh_walk.h — the per-lane walk of the triangle BVH (bvh.h), shared by the wavefront trace
-// (wavefront.hip k_trace_bvh) and the Whitted kernel for scenes beyond LDS (whitted.hip
+// (trace.hip k_trace_bvh) and the Whitted kernel for scenes beyond LDS (whitted.hip
 // k_whitted_bvh), and the small objects' plane cull of the two-level traces.
 //
 // Large triangle scenes (C4): closest hit and any-hit through the host-built BVH (bvh.h).

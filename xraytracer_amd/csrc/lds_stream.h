@@ -1,7 +1,6 @@
 // lds_stream.h — what the one-wave-per-pixel kernels (pixel.hip, whitted.hip) share: the
 // pixel's mt19937 stream in a 624-word circular LDS buffer (x[i] at st[i % 624]; the state
-// k_seed wrote is x[0..623]), generated 128 words at a time, the renderer's invalid-radiance
-// check, and Image::addPixel's ordered sum.
+// k_seed wrote is x[0..623]), generated 128 words at a time, and Image::addPixel's ordered sum.
 #pragma once
 #include "path_common.h"
 
@@ -42,12 +41,6 @@ __device__ __forceinline__ void pix_gen(uint32_t* st, uint32_t g, int lane) {
     st[i0] = b0 ^ mt_mix(a0, a1);
     st[i1] = b1 ^ mt_mix(a1, a2);
     wave_sync();
-}
-
-// integrate(...) / pdf (pinhole pdf 1) and the invalid-radiance check (Src/renderer.cpp:53-73)
-__device__ __forceinline__ bool pix_invalid(v3 r) {
-    return __builtin_isnan(r.x) || __builtin_isnan(r.y) || __builtin_isnan(r.z) || __builtin_isinf(r.x) ||
-           __builtin_isinf(r.y) || __builtin_isinf(r.z) || r.x < 0.0f || r.y < 0.0f || r.z < 0.0f;
 }
 
 // Image::addPixel in sample order for the lanes of vm (lane order), each with value r:

@@ -1,7 +1,8 @@
 // path_common.h — device building blocks shared by the path-tracing kernels
-// (wavefront.hip: wavefront + fused schedules; step_tri.hip: merged-trace triangle
-// schedule): the mt19937 stream restatement, wave utilities, ray/primitive tests, light and
-// BSDF sampling, the camera, and the LDS scene carve of the fused schedules.
+// (shade.hip + trace.hip: wavefront schedule; step.hip: fused schedules; step_tri.hip:
+// merged-trace triangle schedule): the mt19937 stream restatement, wave utilities,
+// ray/primitive tests, light and BSDF sampling, the camera, the steps of the renderer's sample
+// loop every schedule repeats, and the LDS scene carve of the fused schedules.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -579,15 +580,7 @@ __device__ __forceinline__ v3 lambert_sample_f(v3 ng, v3 dpdu, v3 dpdv, RNG& rng
     return local_to_world(mk(x, r1, z), dpdu, ng, dpdv);
 }
 __device__ __forceinline__ v3 lambert_sample(const Surf& S, Rng& rng) {
-    const float r1 = rng.next();
-    const float r2 = rng.next();
-    const float sinTheta = __builtin_sqrtf(1.0f - r1 * r1);
-    const float phi = 2.0f * kPI * r2;
-    float sphi, cphi;
-    glibc_sincosf(phi, sphi, cphi);
-    const float x = sinTheta * cphi;
-    const float z = sinTheta * sphi;
-    return local_to_world(mk(x, r1, z), S.dpdu, S.ng, S.dpdv);
+    return lambert_sample_f(S.ng, S.dpdu, S.dpdv, rng);
 }
 
 __device__ __forceinline__ v3 eval_bxdf(const DObj& ob) {   // Lambert::evaluateBxDF
@@ -617,6 +610,104 @@ __device__ __forceinline__ void camera_ray(const KParams& P, float u, float v, v
                     dir.x * x[2] + dir.y * x[6] + dir.z * x[10]);
     d = normalize(w);
     o = mk(x[12], x[13], x[14]);
+}
+
+// ========================================================== the renderer's sample loop ====
+// The steps of NormalRenderer::doRender (Src/renderer.cpp:29-81) and of the integrators' bounce
+// loops that every schedule repeats, each in the reference's operation order, defined once.
+
+// The camera ray of the sample of pixel (col, row) whose jitter draws are jx, jy
+// (Src/renderer.cpp:44-50).  The caller draws jx, then jy, as two statements (the sampler's order).
+__device__ __forceinline__ void jitter_ray(const KParams& P, uint32_t col, uint32_t row, float jx, float jy, v3& o,
+                                           v3& d) {
+    const float u = div_w(P, (float)(int)col + jx);
+    const float v = div_h(P, (float)(int)row + jy);
+    camera_ray(P, u, v, o, d);
+}
+// ... and the path state integrate() starts that sample with: throughput 1, radiance 0, depth 0
+__device__ __forceinline__ void sample_start(const KParams& P, uint32_t col, uint32_t row, float jx, float jy, v3& o,
+                                             v3& d, v3& thr, v3& rad, uint32_t& depth) {
+    jitter_ray(P, col, row, jx, jy, o, d);
+    thr = mk(1, 1, 1), rad = mk(0, 0, 0);
+    depth = 0;
+}
+
+// The invalid-radiance test on r = integrate(...) / pdf (Src/renderer.cpp:53-73): such a sample
+// is counted and not added to the pixel.
+__device__ __forceinline__ bool radiance_invalid(v3 r) {
+    return __builtin_isnan(r.x) || __builtin_isnan(r.y) || __builtin_isnan(r.z) || __builtin_isinf(r.x) ||
+           __builtin_isinf(r.y) || __builtin_isinf(r.z) || r.x < 0.0f || r.y < 0.0f || r.z < 0.0f;
+}
+
+// Russian roulette past depth 0 (Src/integrator.h:148-155, 224-231, 432-439, 508-515): false =
+// the path ends here; else throughput / Vec3f(p).  (k_shade and k_step hold it open-coded, see
+// there; k_step's volumetric integrators with the quotient through div3s: one division for an
+// achromatic throughput.)
+__device__ __forceinline__ bool russian_roulette(v3& thr, Rng& rng) {
+    const float p = smin((thr.x + thr.y + thr.z) / 3.0f, 1.0f);
+    if (rng.next() >= p) return false;
+    thr = thr / mk(p, p, p);
+    return true;
+}
+
+// The indirect bounce of GIIntegrator / IndirectIntegrator at surface S of object ob
+// (Src/integrator.h:170-179, 272-280): Object::sampleBxDF -> Lambert (no material: 0, no draws),
+// throughput *= f * cos / pdf, and the next ray from the biased hit point.
+__device__ __forceinline__ void lambert_bounce(const DObj& ob, const Surf& S, Rng& rng, v3& thr, v3& o, v3& d) {
+    float pdf = 1.0f;
+    v3 nd = mk(0, 0, 0), fr = mk(0, 0, 0);
+    if (ob.material == 1) {
+        nd = lambert_sample(S, rng);
+        pdf = 1.0f / (2.0f * kPI);
+        fr = eval_bxdf(ob);
+    }
+    const float cosv = smax(0.0f, dot(nd, S.ng));
+    thr = thr * ((fr * cosv) / pdf);
+    o = S.pos + S.ng * 0.01f;
+    d = nd;
+}
+
+// The per-slot fused schedules keep a live slot's path in registers for a launch (k_step_tri
+// through these two; k_step has the same statements in line, see there).
+// slot_load: the stream cursor and generated end, the sample counter, the path (a slot between
+// samples, ST_REGEN, has none: the caller's defaults stay) and the pixel's running sum at px;
+// issues the first RNG prefetch.  slot_store: the same back, and the segment / shadow-ray /
+// reject / stall counts of this launch added to the slot's counters; returns whether the slot's
+// ring runs low (fewer than rng_keep words ahead), for the wave's in-line refill.
+__device__ __forceinline__ void slot_load(const KParams& P, uint32_t s, uint32_t st, const float* px, uint32_t& g,
+                                          Rng& rng, uint32_t& depth, uint32_t& k, v3& thr, v3& rad, v3& o, v3& d,
+                                          v3& acc) {
+    g = P.rng_g[s];
+    rng.c = P.rng_c[s];
+    depth = P.depth[s];
+    k = P.sample_k[s];
+    if (!(st & ST_REGEN)) {
+        thr = xyz(P.thr[s]), rad = xyz(P.rad[s]);
+        o = xyz(P.ray_o[s]), d = xyz(P.ray_d[s]);
+    }
+    acc = mk(px[0], px[1], px[2]);
+    rng.prefetch(g - rng.c);
+}
+__device__ __forceinline__ bool slot_store(const KParams& P, uint32_t s, uint32_t st, float* px, uint32_t g,
+                                           const Rng& rng, uint32_t depth, uint32_t k, v3 thr, v3 rad, v3 o, v3 d,
+                                           v3 acc, uint32_t nseg, uint32_t nsh, uint32_t nrej, uint32_t nstall) {
+    px[0] = acc.x, px[1] = acc.y, px[2] = acc.z;
+    const bool want_req = !(st & (ST_DONE | ST_RNGREQ)) && g - rng.c < P.rng_keep;
+    P.state[s] = st;
+    if (!(st & (ST_DONE | ST_REGEN))) {
+        P.depth[s] = depth;
+        P.thr[s] = pk(thr);
+        P.rad[s] = pk(rad);
+        P.ray_o[s] = pk(o);
+        P.ray_d[s] = pk(d);
+    }
+    P.sample_k[s] = k;
+    P.rng_c[s] = rng.c;
+    if (nseg) P.c_seg[s] += nseg;
+    if (nsh) P.c_shadow[s] += nsh;
+    if (nrej) P.c_rej[s] += nrej;
+    if (nstall) P.c_stall[s] += nstall;
+    return want_req;
 }
 
 

@@ -351,9 +351,9 @@ __global__ __launch_bounds__(BS, XRT_PIX_WAVES) void k_pixel(KParams P, uint32_t
         uint32_t qn = 0, pn = 0, pw = 0;         // DEFER: queued items, pending samples, windows since a flush
         bool s4next = false;                     // the next window is a stride-4 window
 
-        // Image::addPixel in sample order and the invalid-radiance check (lds_stream.h)
+        // Image::addPixel in sample order (lds_stream.h) and the invalid-radiance check
         auto add_in_order = [&](uint64_t vm, v3 r) { pix_add_in_order(sum, lane, acc, vm, r); };
-        auto invalid = [](v3 r) { return pix_invalid(r); };
+        auto invalid = [](v3 r) { return radiance_invalid(r); };
         // DirectIntegrator's light loop for a sample at surface S (Src/integrator.h:94-110), every
         // lane (the shadow rays are a wave walk); `shade`: this lane's sample hit a surface
         auto direct_light = [&](bool shade, const Surf& S, int obj, LdsRng& rng, v3& rad) {
@@ -384,6 +384,7 @@ __global__ __launch_bounds__(BS, XRT_PIX_WAVES) void k_pixel(KParams P, uint32_t
             LdsRng rng{st, act ? it_i[lane] : 0u};
             if (act) {
                 // the item's camera ray again (its jitter words), and its hit record
+                // jitter_ray (path_common.h), open-coded: the call changes this kernel's instructions
                 const float u = div_w(P, (float)(int)col + rng.next());
                 const float v = div_h(P, (float)(int)row + rng.next());
                 v3 ro, rd;
@@ -452,6 +453,7 @@ __global__ __launch_bounds__(BS, XRT_PIX_WAVES) void k_pixel(KParams P, uint32_t
             HitRec h;
             int obj = -1, kind = 0;   // 0 miss, 1 area light, 2 surface
             if (cand) {
+                // jitter_ray, open-coded as above
                 const float u = div_w(P, (float)(int)col + rng.next());
                 const float v = div_h(P, (float)(int)row + rng.next());
                 camera_ray(P, u, v, ro, rd);

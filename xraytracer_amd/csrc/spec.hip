@@ -273,6 +273,7 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_spec(
         // Image::addPixel of a finished sample (Src/renderer.cpp:57-75), lane 0
         auto finish = [&](v3 r0) {
             const v3 r = r0 / 1.0f;
+            // radiance_invalid (path_common.h), open-coded: the call changes this kernel's instructions
             if (__builtin_isnan(r.x) || __builtin_isnan(r.y) || __builtin_isnan(r.z) || __builtin_isinf(r.x) ||
                 __builtin_isinf(r.y) || __builtin_isinf(r.z) || r.x < 0.0f || r.y < 0.0f || r.z < 0.0f) {
                 ++nrej;
@@ -345,9 +346,7 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_spec(
             // (lanes 1-3 hold no extension ray: the candidate takes their o, d and best registers)
             if (want_c) {
                 const float jx = rng.next(), jy = rng.next();
-                const float uu = div_w(P, (float)(int)col + jx);
-                const float vv = div_h(P, (float)(int)row + jy);
-                camera_ray(P, uu, vv, o, d);
+                jitter_ray(P, col, row, jx, jy, o, d);
                 best = camlist_closest(L, make_uint4((uint32_t)cm, (uint32_t)(cm >> 32), (uint32_t)cov, 0u), o, d);
             }
             tick(2);

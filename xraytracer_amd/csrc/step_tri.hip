@@ -4,7 +4,7 @@
 // Same per-pixel sequence as NormalRenderer::doRender + GIIntegrator / DirectIntegrator
 // (Src/renderer.cpp:29-81, Src/integrator.h:82-119, 205-287), one path slot per pixel, path
 // state in registers for `visits` segments per launch.  What differs from k_step_tri
-// (wavefront.hip) is the schedule of the traces:
+// (step.hip) is the schedule of the traces:
 //
 //  * One cooperative trace per segment.  The NEE shadow rays of segment i and the
 //    extension ray of segment i+1 (or the next sample's camera ray) are traced together:
@@ -328,7 +328,7 @@ __host__ __device__ inline BvhStepLayout bvh_step_layout(const KParams& P, uint3
 }
 
 // ------------------------------------------------- two-level trace, phase A ----
-// k_trace_2a (wavefront.hip) with the small objects traced by merged_trace's object-major
+// k_trace_2a (trace.hip) with the small objects traced by merged_trace's object-major
 // pair passes instead of a per-lane object loop: one wave = 64 slots, their extension ray
 // and shadow rays, the small objects' triangles in LDS (KParams::stri, iteration order, so
 // the (t bits << 32 | local index) minimum is the (t, original index) minimum).  The winner's
@@ -565,6 +565,7 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
         // Image::addPixel of a finished sample (Src/renderer.cpp:57-75)
         auto finish = [&](v3 r0) {
             const v3 r = r0 / 1.0f;
+            // radiance_invalid (path_common.h), open-coded: the call changes this kernel's instructions
             if (__builtin_isnan(r.x) || __builtin_isnan(r.y) || __builtin_isnan(r.z) || __builtin_isinf(r.x) ||
                 __builtin_isinf(r.y) || __builtin_isinf(r.z) || r.x < 0.0f || r.y < 0.0f || r.z < 0.0f) {
                 ++nrej;
@@ -576,6 +577,7 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
         };
         // jitter draws + PinholeCamera::sampleRay for the next sample (Src/renderer.cpp:44-50)
         auto start_sample = [&]() {
+            // sample_start (path_common.h), open-coded: the call changes this kernel's instructions
             const float u = div_w(P, (float)(int)col + rng.next());
             const float v = div_h(P, (float)(int)row + rng.next());
             camera_ray(P, u, v, o, d);

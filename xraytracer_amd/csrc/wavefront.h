@@ -1,5 +1,5 @@
 // wavefront.h — device data layout of the MI355X wavefront path tracer, shared by the
-// kernels (wavefront.hip) and the host orchestration (api_*.cpp).
+// kernels (*.hip) and the host orchestration (api_*.cpp).
 //
 // HBM layout (DESIGN.md §Data layout):
 //   scene  : triangles as 3 float4 per triangle {(v0, obj), (e1 = v1-v0, occluder), (e2 = v2-v0, 0)}

@@ -212,13 +212,13 @@ __device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint3
                 uint32_t ci = (o % kMT) + 2u * (uint32_t)lane;
                 if (ci >= kMT) ci -= kMT;
                 LdsRng rng{st, ci};
-                const float u = div_w(P, (float)(int)col + rng.next());
-                const float v = div_h(P, (float)(int)row + rng.next());
+                const float jx = rng.next();
+                const float jy = rng.next();
                 v3 ro, rd;
-                camera_ray(P, u, v, ro, rd);
+                jitter_ray(P, col, row, jx, jy, ro, rd);
                 r = whit_integrate(P, T, ro, rd, C) / 1.0f;
             }
-            const uint64_t vm = __ballot(act && !pix_invalid(r));
+            const uint64_t vm = __ballot(act && !radiance_invalid(r));
             nrej += span - (uint32_t)__builtin_popcountll(vm);
             pix_add_in_order(sum, lane, acc, vm, r);
         }
