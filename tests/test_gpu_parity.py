@@ -432,6 +432,48 @@ def test_two_level_fused_layouts_and_lights(renderer, integ, spw):
     assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
 
 
+def two_light_two_level(w, h, extra=0):
+    """Cornell box, a quad and a triangle light (NL = 2) and a 24 x 24 sphere mesh: 1,152 triangles,
+    above kLargeObjTris, so the scene is two-level.  extra: that many further small objects — sphere
+    meshes at the smallest tessellation (1 x 1, two triangles each) on a grid inside the box."""
+    s = scenes.SceneBundle()
+    s.load_obj(scenes.CORNELL_OBJ)
+    s.add_quad_light("QuadLight", (343.0, 548.0, 227.0), (343.0, 548.0, 332.0), (213.0, 548.0, 227.0),
+                     (25.0, 25.0, 25.0))
+    s.add_triangle_light("TriLight", (100.0, 500.0, 100.0), (150.0, 500.0, 100.0), (100.0, 500.0, 150.0),
+                         (10.0, 5.0, 2.0))
+    s.add_sphere_mesh("sphere_mesh", (150.0, 420.0, 400.0), 90.0, 24, 24, (0.58, 0.58, 0.58))
+    for k in range(extra):
+        s.add_sphere_mesh(f"small_{k}", (60.0 + 70.0 * (k % 7), 40.0 + 60.0 * (k // 7), 120.0 + 30.0 * (k % 5)), 20.0,
+                          1, 1, (0.7, 0.4, 0.3))
+    s.flatten()
+    s.camera = scenes.pinhole(scenes.CORNELL_C2W, 60.0, w, h)
+    return s
+
+
+def check_two_level_wavefront(renderer, s, integ, deep):
+    img, ref, st = render_both(renderer, s, 48, 30, 3, integrator=integ, deep=deep, schedule="wavefront")
+    compare(img, ref)
+    g = renderer.stats
+    assert g.schedule == abi.XRT_SCHED_WAVEFRONT and g.launches[abi.XRT_K_DEEP] > 0 and g.shadow_rays > 0
+    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+
+
+@pytest.mark.parametrize("integ", ["gi", "direct"])
+@pytest.mark.parametrize("deep", ["single", "quad"])
+def test_two_level_wavefront_two_lights(renderer, integ, deep):
+    """The wavefront two-level trace with two area lights: phase A by pair passes
+    (k_trace_2a_coop<kMaxLights>) and both phase-B kernels with deep-queue entries of shadow kinds 1
+    and 2, bit-exact with counters equal."""
+    check_two_level_wavefront(renderer, two_light_two_level(48, 30), integ, deep)
+
+
+def test_two_level_wavefront_many_small_objects(renderer):
+    """More small objects than kMergedMaxObjs (32): no pair-pass records (KParams::sstep null), so a
+    render's phase A is the per-lane k_trace_2a<kMaxLights>."""
+    check_two_level_wavefront(renderer, two_light_two_level(48, 30, extra=30), "gi", "quad")
+
+
 def test_triangle_light_and_two_lights(renderer, sched):
     s = scenes.SceneBundle()
     s.load_obj(scenes.CORNELL_OBJ)

@@ -14,6 +14,8 @@ import pyoracle
 from xraytracer_amd import scenes
 from xraytracer_amd.renderer import HipRenderer
 
+from test_gpu_parity import two_light_two_level
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,6 +68,27 @@ def test_query_matches_oracle(name):
     ref = pyoracle.query(s, rays, tmax=tmax, occluded=True)
     assert [h.hit for h in got] == [h.hit for h in ref]
     assert sum(h.hit for h in ref) > 0
+    r.close()
+
+
+def test_query_two_lights_two_level():
+    """Both queries over the two-light two-level scene: k_trace_2a<kMaxLights> and the deep walk."""
+    s = two_light_two_level(32, 18)
+    assert s.desc.n_lights == 2
+    rng = np.random.default_rng(23)
+    rays = random_rays(rng, 4000, (0.0, 0.0, 0.0), (556.0, 548.0, 559.0), (278.0, 274.4, -750.0))
+    tmax = rng.uniform(0.0, 800.0, len(rays)).astype(np.float32)
+    r = HipRenderer(1, device=0)
+    got = r.query(s, rays)
+    ref = pyoracle.query(s, rays)
+    assert sum(h.hit for h in ref) > 500
+    for k in range(len(rays)):
+        assert np.array_equal(record(got[k]), record(ref[k])), (k, rays[k])
+    got = r.query(s, rays, tmax=tmax, occluded=True)
+    ref = pyoracle.query(s, rays, tmax=tmax, occluded=True)
+    hits = [h.hit for h in ref]
+    assert [h.hit for h in got] == hits
+    assert 0 < sum(hits) < len(hits)
     r.close()
 
 

@@ -154,38 +154,17 @@ __global__ __launch_bounds__(kWhitBlock) void k_aov(KParams P, AovOut A, uint32_
 template <bool TWO, typename SE>
 __global__ __launch_bounds__(kWhitBlock) void k_aov_bvh(KParams P, AovOut A, uint32_t* __restrict__ work) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_aov_bvh[];
-    char* lb = reinterpret_cast<char*>(lds_aov_bvh);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const WhitBvhLayout Lo = whit_bvh_layout(P);
-    const int ntop = P.bvh_nodes < (int)kBvhTopNodes ? P.bvh_nodes : (int)kBvhTopNodes;
-    f4* top = lds_aov_bvh;
-    f4* ltri = reinterpret_cast<f4*>(lb + Lo.tri);
-    DObjBox* lbox = reinterpret_cast<DObjBox*>(lb + Lo.box);
-    DObjPlane* lpl = reinterpret_cast<DObjPlane*>(lb + Lo.plane);
-    lds_copy(top, P.bvh_node, 4 * ntop, tid, kWhitBlock);
-    if (TWO) {
-        lds_copy(ltri, P.stri, 3 * P.n_stri, tid, kWhitBlock);
-        lds_copy(lbox, P.sbox, P.n_sobj, tid, kWhitBlock);
-        lds_copy(lpl, P.splane, P.n_sobj, tid, kWhitBlock);
-    }
-    SE* stk = reinterpret_cast<SE*>(lb + Lo.stack) + tid;
-    uint32_t* st = reinterpret_cast<uint32_t*>(lb + Lo.wave + (tid >> 6) * kWhitWaveLds);
-    __syncthreads();
-    const WhitBvh<TWO, SE> T{P, top, ntop, stk, ltri, lbox, lpl, P.objs};
-    aov_pixels(P, A, T, st, work, lane);
+    const auto B = whit_bvh_setup<TWO, SE>(P, reinterpret_cast<char*>(lds_aov_bvh), threadIdx.x);
+    aov_pixels(P, A, B.T, B.st, work, threadIdx.x & 63);
 }
 
-// persistent grid: as many blocks as fit on the device at once, at most one wave per pixel
+// one launch over the shard's pixels: a persistent grid, at most one wave per pixel
 template <typename K>
 static hipError_t aov_launch(K kern, size_t lds, const KParams& P, const AovOut& A, uint32_t* work, hipStream_t st) {
-    int dev = 0, ncu = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWhitBlock, lds);
+    uint32_t blocks = 0;
+    const hipError_t e = persistent_blocks(kern, kWhitBlock, lds, P.n_slots, &blocks);
     if (e != hipSuccess) return e;
-    const uint64_t want = ((uint64_t)P.n_slots + kWhitBlock / 64 - 1) / (kWhitBlock / 64);
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(kWhitBlock), lds, st, P, A, work);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWhitBlock), lds, st, P, A, work);
     return hipGetLastError();
 }
 
@@ -195,21 +174,13 @@ hipError_t launch_aov(const KParams& P, const AovOut& A, uint32_t* work, hipStre
     const int which = aov_kernel(P);
     if (!which || !A.obj_albedo) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
-    if (which == 1) {
-        const size_t lds = whit_lds_bytes(P);
-        switch (P.scene_kind) {
-            case SCN_TRI: return aov_launch(k_aov<SCN_TRI>, lds, P, A, work, st);
-            case SCN_SPHERE: return aov_launch(k_aov<SCN_SPHERE>, lds, P, A, work, st);
-            default: return aov_launch(k_aov<SCN_MIXED>, lds, P, A, work, st);
-        }
-    }
-    const size_t lds = whit_bvh_lds_bytes(P);
-    const bool small = P.bvh_nodes <= 0x10000;   // node indices below 2^16: 16-bit stack entries
-    if (P.two_level)
-        return small ? aov_launch(k_aov_bvh<true, uint16_t>, lds, P, A, work, st)
-                     : aov_launch(k_aov_bvh<true, uint32_t>, lds, P, A, work, st);
-    return small ? aov_launch(k_aov_bvh<false, uint16_t>, lds, P, A, work, st)
-                 : aov_launch(k_aov_bvh<false, uint32_t>, lds, P, A, work, st);
+    if (which == 1)
+        return with_scene_kind(P.scene_kind, [&](auto scn) {
+            return aov_launch(k_aov<decltype(scn)::value>, whit_lds_bytes(P), P, A, work, st);
+        });
+    return with_whit_bvh(P, [&](auto two, auto se) {
+        return aov_launch(k_aov_bvh<decltype(two)::value, decltype(se)>, whit_bvh_lds_bytes(P), P, A, work, st);
+    });
 }
 
 }  // namespace xrt

@@ -1,6 +1,9 @@
-// bvh_walk.h — the per-lane walk of the triangle BVH (bvh.h), shared by the wavefront trace
-// (trace.hip k_trace_bvh) and the Whitted kernel for scenes beyond LDS (whitted.hip
-// k_whitted_bvh), and the small objects' plane cull of the two-level traces.
+// bvh_walk.h — what the kernels that walk the triangle BVH (bvh.h) share:
+//   BvhLds, bvh_lds / bvh4_lds, with_stack_entry, bvh_top_load : the BVH's share of LDS — the top
+//       nodes and the traversal stacks — as launchers size it and kernels carve it (trace.hip
+//       k_trace_bvh, k_trace_deep4, k_trace_deep4q; whit_trace.h WhitBvhLayout)
+//   bvh_leaf, bvh_trace : the per-lane walk (k_trace_bvh; whit_trace.h WhitBvh)
+//   plane_away_w        : the small objects' plane cull of the two-level traces
 //
 // Large triangle scenes (C4): closest hit and any-hit through the host-built BVH (bvh.h).
 // Exactness: every node box is padded beyond the float error of a Moller-Trumbore hit, a
@@ -16,6 +19,34 @@
 #include "path_common.h"
 
 namespace xrt {
+
+// The BVH's share of a block's LDS: the first ntop nodes (breadth-first: the top of the tree) at
+// the start, then from byte `stack` the traversal stacks, whose entries are node indices —
+// 16-bit when every index fits (half the LDS per thread), else 32-bit.
+struct BvhLds {
+    int ntop;               // nodes
+    uint32_t node, entry;   // bytes per node; bytes per stack entry
+    __host__ __device__ uint32_t stack() const { return (uint32_t)ntop * node; }   // byte offset of the stacks
+    // with `stacks` stacks of `depth` entries each
+    __host__ __device__ size_t bytes(int depth, int stacks) const { return stack() + (size_t)depth * stacks * entry; }
+};
+__host__ __device__ inline BvhLds bvh_lds_of(int nodes, uint32_t node_bytes) {
+    return {nodes < (int)kBvhTopNodes ? nodes : (int)kBvhTopNodes, node_bytes, nodes <= 0x10000 ? 2u : 4u};
+}
+__host__ __device__ inline BvhLds bvh_lds(const KParams& P) { return bvh_lds_of(P.bvh_nodes, sizeof(BvhNode)); }
+__host__ __device__ inline BvhLds bvh4_lds(const KParams& P) { return bvh_lds_of(P.bvh4_nodes, sizeof(Bvh4Node)); }
+// fn(SE{}) with the stack entry type the layout names
+template <typename F>
+auto with_stack_entry(const BvhLds& B, F&& fn) {
+    return B.entry == 2 ? fn(uint16_t{}) : fn(uint32_t{});
+}
+// the block copies the top nodes to `top`, the start of its dynamic LDS (the caller syncs);
+// returns thread 0's stack base
+template <typename SE>
+__device__ __forceinline__ SE* bvh_top_load(void* top, const f4* nodes, const BvhLds& B, int tid, int stride = kBlock) {
+    for (int q = tid; q < B.ntop * (int)(B.node / sizeof(f4)); q += stride) static_cast<f4*>(top)[q] = nodes[q];
+    return reinterpret_cast<SE*>(static_cast<char*>(top) + B.stack());
+}
 
 template <bool ANY>
 __device__ __forceinline__ bool bvh_leaf(const KParams& P, int first, int count, v3 o, v3 d, float tmax, float& bt,

@@ -1,5 +1,8 @@
 // launch.h — host-callable kernel launchers and their eligibility / sizing helpers, grouped
-// below by the unit (*.hip) that defines them.
+// below by the unit (*.hip) that defines them, after what the launchers themselves share: the
+// runtime-value-to-template dispatch (with_const, with_scene_kind, with_integrator) and the grid
+// of the persistent pixel kernels (persistent_blocks).  The BVH kernels' dispatch on the stack
+// entry type is with_stack_entry (bvh_walk.h) and with_whit_bvh (whit_trace.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +44,21 @@ template <typename F>
 auto with_integrator(int integrator, F&& fn) {
     return with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_VPT, XRT_INTEGRATOR_INDIRECT, XRT_INTEGRATOR_NORMAL,
                       XRT_INTEGRATOR_VPT_NEE, XRT_INTEGRATOR_GI>(integrator, fn);
+}
+// Grid of a persistent kernel that takes the shard's n_slots pixels from a counter, one wave per
+// pixel at a time: as many blocks as fit on the device at once (the occupancy of `kernel` at
+// `block` threads and `lds` dynamic LDS bytes, times the CUs), at most one wave per pixel, at
+// least one block.
+template <typename K>
+hipError_t persistent_blocks(K kernel, int block, size_t lds, uint32_t n_slots, uint32_t* blocks) {
+    int dev = 0, ncu = 0, per_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds);
+    if (e != hipSuccess) return e;
+    const uint64_t want = ((uint64_t)n_slots + block / 64 - 1) / (block / 64);
+    *blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------------- frame.hip ----
@@ -86,7 +104,7 @@ hipError_t launch_refill(const KParams& P, const uint32_t* count, uint32_t* zero
 // the merged schedule's refill (leaves ST_RNGREQ to the merged kernel; see step_tri.hip)
 hipError_t launch_refill_merged(const KParams& P, const uint32_t* count, uint32_t* zero_count, hipStream_t st);
 // phase A of a two-level trace with the small objects traced by the merged pair passes
-// (launch_trace calls it when P.sstep is set)
+// (launch_trace calls it when P.sstep is set; the one-light or kMaxLights build, as launch_trace's)
 hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
                                 uint32_t blocks, hipStream_t st);
 // merged-trace triangle schedule: eligibility, RNG words one segment may

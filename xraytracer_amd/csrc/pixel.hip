@@ -595,16 +595,10 @@ static hipError_t pixel_i(const KParams& P, uint32_t* work, hipStream_t st) {
     constexpr int BS = pix_block(SCN, INTEG);
     const size_t lds = pix_lds_bytes(P);
     auto kern = k_pixel<SCN, INTEG, BS>;
-    // persistent grid: as many blocks as fit on the device at once (LDS and VGPR bound), at
-    // most one wave per pixel
-    int dev = 0, ncu = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BS, lds);
+    uint32_t blocks = 0;   // persistent grid, at most one wave per pixel
+    const hipError_t e = persistent_blocks(kern, BS, lds, P.n_slots, &blocks);
     if (e != hipSuccess) return e;
-    const uint64_t want = ((uint64_t)P.n_slots + BS / 64 - 1) / (BS / 64);
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(BS), lds, st, P, work);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, st, P, work);
     return hipGetLastError();
 }
 
@@ -617,11 +611,7 @@ static hipError_t pixel_s(const KParams& P, uint32_t* work, hipStream_t st) {
 hipError_t launch_pixel(const KParams& P, uint32_t* work, hipStream_t st) {
     if (!use_pixel(P)) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
-    switch (P.scene_kind) {
-        case SCN_TRI: return pixel_s<SCN_TRI>(P, work, st);
-        case SCN_SPHERE: return pixel_s<SCN_SPHERE>(P, work, st);
-        default: return pixel_s<SCN_MIXED>(P, work, st);
-    }
+    return with_scene_kind(P.scene_kind, [&](auto scn) { return pixel_s<decltype(scn)::value>(P, work, st); });
 }
 
 }  // namespace xrt

@@ -33,6 +33,7 @@
 #include "launch.h"
 #include "merged.h"
 #include "path_common.h"
+#include "trace_common.h"
 
 namespace xrt {
 
@@ -346,70 +347,32 @@ __global__ __launch_bounds__(kBlock, XRT_2A_WAVES) void k_trace_2a_coop(KParams 
     lds_copy(const_cast<f4*>(L.tri), P.stri, 3 * P.n_stri, tid);
     zero_parts(P, zero_count);
     __syncthreads();
-    const f4 r0 = P.bvh_node[0], r1 = P.bvh_node[1], r2 = P.bvh_node[2], r3 = P.bvh_node[3];   // root
     const PartIter it = part_iter(P, count, kBlock);
-    uint32_t* dq = P.deep + (size_t)it.p * P.deep_cap;
+    const PhaseA A = phase_a_begin(P, it);
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
-        const uint32_t i = base + tid;
-        const bool valid = i < it.n;
-        const uint32_t s = valid ? list[it.p * P.part_cap + i] : 0;
-        const uint32_t st = valid ? P.state[s] : 0;
-        const bool want = (st & ST_RAY) != 0;
-        const uint32_t smask = (st >> ST_SHADOW_SHIFT) & ((1u << NL) - 1u);
-        v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-        if (want) o = xyz(P.ray_o[s]), d = xyz(P.ray_d[s]);
-        v3 so[NL + 1], sd[NL + 1];
-        float stm[NL + 1];
-#pragma unroll
-        for (int l = 0; l <= NL; ++l) so[l] = sd[l] = mk(0, 0, 0), stm[l] = 0.0f;
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-            if (smask & (1u << l)) {
-                const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                so[l] = xyz(a), stm[l] = a.w;
-                sd[l] = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-            }
-        }
+        const SlotRays<NL, NL + 1> R = load_slot_rays<NL, NL + 1>(P, list, it, base + tid);
         unsigned long long best;
-        uint32_t occ;
-        merged_trace<NL>(SO, L, W, lane, want, o, d, smask, so, sd, stm, best, occ);
-        float bt = kINF, bu = 0.0f, bv = 0.0f;
-        int bk = -1;
-        if (want && best != ~0ull) {
+        SlotHit H;
+        merged_trace<NL>(SO, L, W, lane, R.want, R.o, R.d, R.smask, R.so, R.sd, R.stmax, best, H.occ);
+        if (R.want && best != ~0ull) {
             const int hk = (int)(uint32_t)best;
-            (void)ray_tri(o, d, xyz(L.tri[3 * hk]), xyz(L.tri[3 * hk + 1]), xyz(L.tri[3 * hk + 2]), bt, bu, bv);
-            bk = __float_as_int(L.tri[3 * hk + 2].w);
+            (void)ray_tri(R.o, R.d, xyz(L.tri[3 * hk]), xyz(L.tri[3 * hk + 1]), xyz(L.tri[3 * hk + 2]), H.t, H.u, H.v);
+            H.k = __float_as_int(L.tri[3 * hk + 2].w);
         }
-        const v3 inv = rcp3(d);
-        const bool dext = want && root_overlap(r0, r1, r2, r3, o, inv, bt);
-        uint32_t dsh = 0;
-#pragma unroll
-        for (int l = 0; l < NL; ++l)
-            if ((smask & ~occ & (1u << l)) && root_overlap(r0, r1, r2, r3, so[l], rcp3(sd[l]), stm[l])) dsh |= 1u << l;
-        if (valid) {
-            if (want) P.hit[s] = make_float4(bt, bu, bv, __int_as_float(bk));
-            if (smask) P.occ[s] = occ & smask;
-        }
-        wave_append(valid && dext, s * 8u, dq, P.deep_count + it.p, lane);
-#pragma unroll
-        for (int l = 0; l < NL; ++l)
-            wave_append(valid && ((dsh >> l) & 1u), s * 8u + 1u + (uint32_t)l, dq + P.part_cap,
-                        P.deep_count + 2 * kMaxParts + it.p, lane);
+        H.occ &= R.smask;
+        phase_a_finish(P, A, R, rcp3(R.d), H, lane);
         wave_sync();   // W is rewritten by the next round's rays
     }
 }
 
 hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
                                 uint32_t blocks, hipStream_t st) {
-    if (P.n_lights <= 1) {
-        const size_t lds = (size_t)P.n_stri * 3 * sizeof(f4) + (kBlock / 64) * sizeof(MergedWave<1>);
-        hipLaunchKernelGGL((k_trace_2a_coop<1>), dim3(blocks), dim3(kBlock), lds, st, P, *P.sstep, list, count, zero);
-    } else {
-        const size_t lds = (size_t)P.n_stri * 3 * sizeof(f4) + (kBlock / 64) * sizeof(MergedWave<kMaxLights>);
-        hipLaunchKernelGGL((k_trace_2a_coop<kMaxLights>), dim3(blocks), dim3(kBlock), lds, st, P, *P.sstep, list, count,
-                           zero);
-    }
-    return hipGetLastError();
+    return with_const<1, kMaxLights>(P.n_lights <= 1 ? 1 : kMaxLights, [&](auto nl) {
+        constexpr int NL = decltype(nl)::value;
+        const size_t lds = (size_t)P.n_stri * 3 * sizeof(f4) + (kBlock / 64) * sizeof(MergedWave<NL>);
+        hipLaunchKernelGGL((k_trace_2a_coop<NL>), dim3(blocks), dim3(kBlock), lds, st, P, *P.sstep, list, count, zero);
+        return hipGetLastError();
+    });
 }
 
 // --------------------------------------------------------------- RNG refills ----

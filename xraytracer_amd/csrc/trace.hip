@@ -5,12 +5,16 @@
 //   k_trace_bvh   : large triangle scenes through the host-built BVH (bvh.h, bvh_walk.h)
 //   k_trace_2a, k_trace_deep4, k_trace_deep4q : the two-level trace (small objects, then the
 //                   BVH walk of the queued rays alone)
+// What these kernels share is defined once in trace_common.h (the slot ray load, the small-object
+// scan, phase A's tail, phase B's queue view and ray fetch; k_trace_2a_coop in step_tri.hip uses
+// the same) and bvh_walk.h (the BVH's share of LDS, the per-lane walk).
 // The ray queries (xrt_query) run through the same kernels: k_query_in turns the caller's rays
 // into slots, launch_trace traces them, k_query_out rebuilds IntersectInfo from the records.
 #include "bvh.h"
 #include "bvh_walk.h"
 #include "launch.h"
 #include "path_common.h"
+#include "trace_common.h"
 
 namespace xrt {
 
@@ -25,29 +29,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
     const PartIter it = part_iter(P, count, kBlock);
     const int tid = threadIdx.x;
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
-        const uint32_t i = base + tid;
-        const bool valid = i < it.n;
-        const uint32_t s = valid ? list[it.p * P.part_cap + i] : 0;
-        const uint32_t st = valid ? P.state[s] : 0;
-        const bool want = (st & ST_RAY) != 0;
-        const uint32_t smask = (st >> ST_SHADOW_SHIFT) & ((1u << NL) - 1u);
-        v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-        if (want) {
-            o = xyz(P.ray_o[s]);
-            d = xyz(P.ray_d[s]);
-        }
-        v3 so[NL], sd[NL];
-        float stmax[NL];
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-            so[l] = mk(0, 0, 0), sd[l] = mk(0, 0, 0), stmax[l] = 0.0f;
-            if (smask & (1u << l)) {
-                const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                so[l] = xyz(a);
-                stmax[l] = a.w;
-                sd[l] = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-            }
-        }
+        const SlotRays<NL> R = load_slot_rays<NL>(P, list, it, base + tid);
         uint32_t occ = 0;
         float best_t = kINF, bu = 0.0f, bv = 0.0f;
         int best = -1;
@@ -67,9 +49,9 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
                     for (int k = 0; k < nt; ++k) {
                         const f4 A = lds_tri[3 * k], B = lds_tri[3 * k + 1], Cc = lds_tri[3 * k + 2];
                         const v3 v0 = xyz(A), e1 = xyz(B), e2 = xyz(Cc);
-                        if (want) {
+                        if (R.want) {
                             float t, u, v;
-                            if (ray_tri(o, d, v0, e1, e2, t, u, v) && t < best_t) {
+                            if (ray_tri(R.o, R.d, v0, e1, e2, t, u, v) && t < best_t) {
                                 best_t = t, bu = u, bv = v, best = tb + k;
                                 if (SCN == SCN_MIXED) surf = best, surf_t = t, surf_u = u, surf_v = v, dp = best, dp_u = u, dp_v = v;
                             }
@@ -77,9 +59,9 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
                         if (B.w != 0.0f) {  // occluder (object without an area light)
 #pragma unroll
                             for (int l = 0; l < NL; ++l) {
-                                if ((smask & (1u << l)) && !(occ & (1u << l))) {
+                                if ((R.smask & (1u << l)) && !(occ & (1u << l))) {
                                     float t, u, v;
-                                    if (ray_tri(so[l], sd[l], v0, e1, e2, t, u, v) && t < stmax[l]) occ |= 1u << l;
+                                    if (ray_tri(R.so[l], R.sd[l], v0, e1, e2, t, u, v) && t < R.stmax[l]) occ |= 1u << l;
                                 }
                             }
                         }
@@ -97,9 +79,9 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
                     for (int k = 0; k < nt; ++k) {
                         const f4 S = lds_sph[k];
                         const v3 c = xyz(S);
-                        if (want) {
+                        if (R.want) {
                             float t;
-                            if (sphere_hit(o, d, c, S.w, t) && t < best_t) {
+                            if (sphere_hit(R.o, R.d, c, S.w, t) && t < best_t) {
                                 best_t = t, bu = 0.0f, bv = 0.0f, best = (1 << 28) | (tb + k);
                                 if (SCN == SCN_MIXED) surf = best, surf_t = t;
                             }
@@ -107,9 +89,9 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
                         if (lds_sobj[k] & (1 << 30)) {
 #pragma unroll
                             for (int l = 0; l < NL; ++l) {
-                                if ((smask & (1u << l)) && !(occ & (1u << l))) {
+                                if ((R.smask & (1u << l)) && !(occ & (1u << l))) {
                                     float t;
-                                    if (sphere_hit(so[l], sd[l], c, S.w, t) && t < stmax[l]) occ |= 1u << l;
+                                    if (sphere_hit(R.so[l], R.sd[l], c, S.w, t) && t < R.stmax[l]) occ |= 1u << l;
                                 }
                             }
                         }
@@ -118,24 +100,24 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
             } else if (SCN == SCN_MIXED && seg.kind == SEG_BOX) {
                 for (int b = seg.first; b < seg.first + seg.count; ++b) {
                     const v3 pmin = xyz(P.box[2 * b]), pmax = xyz(P.box[2 * b + 1]);
-                    if (want) {
+                    if (R.want) {
                         float t0, tt1;
-                        if (box_hit(o, d, pmin, pmax, t0, tt1)) best_t = t0, t1 = tt1, best = (2 << 28) | b;
+                        if (box_hit(R.o, R.d, pmin, pmax, t0, tt1)) best_t = t0, t1 = tt1, best = (2 << 28) | b;
                     }
                     // BoxMesh::occluded returns true unconditionally (Src/primitive.h:266-268)
-                    occ |= smask;
+                    occ |= R.smask;
                 }
             }
         }
-        if (valid) {
-            if (want) {
-                P.hit[s] = make_float4(best_t, bu, bv, __int_as_float(best));
+        if (R.valid) {
+            if (R.want) {
+                P.hit[R.s] = make_float4(best_t, bu, bv, __int_as_float(best));
                 if (SCN == SCN_MIXED) {
-                    P.hit2[s] = make_float4(t1, __int_as_float(surf), __int_as_float(dp), surf_t);
-                    P.hit3[s] = make_float4(surf_u, surf_v, dp_u, dp_v);
+                    P.hit2[R.s] = make_float4(t1, __int_as_float(surf), __int_as_float(dp), surf_t);
+                    P.hit3[R.s] = make_float4(surf_u, surf_v, dp_u, dp_v);
                 }
             }
-            if (smask) P.occ[s] = occ;
+            if (R.smask) P.occ[R.s] = occ;
         }
     }
 }
@@ -155,18 +137,16 @@ __global__ __launch_bounds__(kBlock) void k_trace(KParams P, const uint32_t* __r
 template <int NL, typename SE>
 __global__ __launch_bounds__(kBlock) void k_trace_bvh(KParams P, const uint32_t* __restrict__ list,
                                                        const uint32_t* __restrict__ count, uint32_t* zero_count) {
-    // LDS: the top min(bvh_nodes, kBvhTopNodes) nodes, then P.bvh_stack * kBlock stack
-    // entries of SE (sized to the tree)
+    // LDS (bvh_lds): the top nodes, then P.bvh_stack * kBlock stack entries of SE
     extern __shared__ uint32_t bvh_stack_lds[];
     const int tid = threadIdx.x;
-    const int ntop = P.bvh_nodes < (int)kBvhTopNodes ? P.bvh_nodes : (int)kBvhTopNodes;
-    f4* top = reinterpret_cast<f4*>(bvh_stack_lds);
-    for (int q = tid; q < 4 * ntop; q += kBlock) top[q] = P.bvh_node[q];
-    SE* stack = reinterpret_cast<SE*>(bvh_stack_lds + 16 * ntop);
+    const BvhLds B = bvh_lds(P);
+    const f4* top = reinterpret_cast<const f4*>(bvh_stack_lds);
+    const int ntop = B.ntop;
+    SE* stk = bvh_top_load<SE>(bvh_stack_lds, P.bvh_node, B, tid) + tid;
     __syncthreads();
     zero_parts(P, zero_count);
     const PartIter it = part_iter(P, count, kBlock);
-    SE* stk = stack + tid;
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
         const uint32_t i = base + tid;
         if (i >= it.n) continue;
@@ -200,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_bvh(KParams P, const uint32_t*
 // blocks around a 51,200-triangle sphere): one wave's rays mostly bounce between the small
 // objects, but a single lane whose segment passes the big mesh makes the whole wave walk
 // its BVH (k_trace_bvh: lane utilisation 0.12).  Phase A (k_trace_2a) scans the small
-// objects as k_trace_small does (LDS, in iteration order, strict t < best: the
+// objects as k_trace_small does (small_scan: LDS, in iteration order, strict t < best: the
 // lexicographic (t, index) minimum among them), then queues only the rays whose segment
 // [0, best t] (any-hit: [0, tmax], if not yet occluded) overlaps the BVH root; phase B
 // (k_trace_deep) walks the BVH for the queued rays alone — full waves of deep rays — and
@@ -217,84 +197,14 @@ __global__ __launch_bounds__(kBlock) void k_trace_2a(KParams P, const uint32_t* 
     for (int q = tid; q < 3 * P.n_stri; q += kBlock) ltri[q] = P.stri[q];
     for (int q = tid; q < P.n_sobj; q += kBlock) lbox[q] = P.sbox[q], lpl[q] = P.splane[q];
     __syncthreads();
-    const f4 r0 = P.bvh_node[0], r1 = P.bvh_node[1], r2 = P.bvh_node[2], r3 = P.bvh_node[3];   // root
     const PartIter it = part_iter(P, count, kBlock);
-    uint32_t* dq = P.deep + (size_t)it.p * P.deep_cap;
+    const PhaseA A = phase_a_begin(P, it);
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
-        const uint32_t i = base + tid;
-        const bool valid = i < it.n;
-        const uint32_t s = valid ? list[it.p * P.part_cap + i] : 0;
-        const uint32_t st = valid ? P.state[s] : 0;
-        const bool want = (st & ST_RAY) != 0;
-        const uint32_t smask = (st >> ST_SHADOW_SHIFT) & ((1u << NL) - 1u);
-        v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-        if (want) {
-            o = xyz(P.ray_o[s]);
-            d = xyz(P.ray_d[s]);
-        }
-        v3 so[NL], sd[NL];
-        float stmax[NL];
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-            so[l] = mk(0, 0, 0), sd[l] = mk(0, 0, 0), stmax[l] = 0.0f;
-            if (smask & (1u << l)) {
-                const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                so[l] = xyz(a);
-                stmax[l] = a.w;
-                sd[l] = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-            }
-        }
-        const v3 inv = rcp3(d);
-        uint32_t occ = 0;
-        float best_t = kINF, bu = 0.0f, bv = 0.0f;
-        int best = -1;
-        for (int ob = 0; ob < P.n_sobj; ++ob) {
-            const DObjBox B = lbox[ob];
-            const DObjPlane pl = lpl[ob];
-            const int cnt = B.count_occ & 0x7fffffff;
-            const bool occluder = B.count_occ < 0;
-            const bool ne = want && !plane_away_w(o, d, pl) && box_overlap(o, inv, B, best_t);
-            uint32_t nsm = 0;
-            if (occluder) {
-#pragma unroll
-                for (int l = 0; l < NL; ++l)
-                    if ((smask & ~occ & (1u << l)) && !plane_away_w(so[l], sd[l], pl) &&
-                        box_overlap(so[l], rcp3(sd[l]), B, stmax[l]))
-                        nsm |= 1u << l;
-            }
-            if (__ballot(ne || nsm) == 0) continue;
-            for (int k = B.first; k < B.first + cnt; ++k) {
-                const v3 v0 = xyz(ltri[3 * k]), e1 = xyz(ltri[3 * k + 1]);
-                const f4 E2 = ltri[3 * k + 2];
-                const v3 e2 = xyz(E2);
-                if (ne) {
-                    float t, u, v;
-                    if (ray_tri(o, d, v0, e1, e2, t, u, v) && t < best_t)
-                        best_t = t, bu = u, bv = v, best = __float_as_int(E2.w);
-                }
-#pragma unroll
-                for (int l = 0; l < NL; ++l) {
-                    if (nsm & ~occ & (1u << l)) {
-                        float t, u, v;
-                        if (ray_tri(so[l], sd[l], v0, e1, e2, t, u, v) && t < stmax[l]) occ |= 1u << l;
-                    }
-                }
-            }
-        }
-        const bool dext = want && root_overlap(r0, r1, r2, r3, o, inv, best_t);
-        uint32_t dsh = 0;
-#pragma unroll
-        for (int l = 0; l < NL; ++l)
-            if ((smask & ~occ & (1u << l)) && root_overlap(r0, r1, r2, r3, so[l], rcp3(sd[l]), stmax[l])) dsh |= 1u << l;
-        if (valid) {
-            if (want) P.hit[s] = make_float4(best_t, bu, bv, __int_as_float(best));
-            if (smask) P.occ[s] = occ;
-        }
-        wave_append(valid && dext, s * 8u, dq, P.deep_count + it.p, lane);
-#pragma unroll
-        for (int l = 0; l < NL; ++l)
-            wave_append(valid && ((dsh >> l) & 1u), s * 8u + 1u + (uint32_t)l, dq + P.part_cap,
-                        P.deep_count + 2 * kMaxParts + it.p, lane);
+        const SlotRays<NL> R = load_slot_rays<NL>(P, list, it, base + tid);
+        const v3 inv = rcp3(R.d);
+        SlotHit H;
+        small_scan<true, true>(R, inv, ltri, lbox, lpl, P.n_sobj, H);
+        phase_a_finish(P, A, R, inv, H, lane);
     }
 }
 
@@ -328,7 +238,7 @@ __device__ __forceinline__ bool bvh_leaf_batch(const KParams& P, int first, int 
 // Phase B: the queued rays walk the BVH's 4-wide form (bvh.h Bvh4Node: a step fetches four
 // child boxes, the tree is about half as deep as the binary one), with dynamic ray fetch —
 // a lane whose ray is done takes the next queued ray of its partition (one atomic per wave
-// per refill, when at least 16 lanes are idle or the wave is empty), so lanes stay busy
+// per refill, when at least 16 lanes are idle or the wave is empty: deep_fetch), so lanes stay busy
 // until the queue drains (a static assignment measured lane utilisation 0.095: most queued
 // rays cross the mesh's box and leave after a few nodes, a few descend to the surface).
 // One loop iteration = one node per active lane: the four children tested against [0, lim]
@@ -341,94 +251,54 @@ template <typename SE>
 __global__ __launch_bounds__(kBlock, XRT_DEEP_WAVES) void k_trace_deep4(KParams P) {
     extern __shared__ uint32_t bvh_stack_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int ntop = P.bvh4_nodes < (int)kBvhTopNodes ? P.bvh4_nodes : (int)kBvhTopNodes;
-    f4* top = reinterpret_cast<f4*>(bvh_stack_lds);
-    for (int q = tid; q < 8 * ntop; q += kBlock) top[q] = P.bvh4[q];
-    SE* stk = reinterpret_cast<SE*>(bvh_stack_lds + 32 * ntop) + tid;
+    const BvhLds B = bvh4_lds(P);
+    const f4* top = reinterpret_cast<const f4*>(bvh_stack_lds);
+    const int ntop = B.ntop;
+    SE* stk = bvh_top_load<SE>(bvh_stack_lds, P.bvh4, B, tid) + tid;
     __syncthreads();
-    const uint32_t p = blockIdx.x % P.n_part;
-    // extension rays first, then shadow rays (queued apart by phase A), so a wave's lanes
-    // mostly run the same kind of walk (closest hit or any hit) at a time
-    const uint32_t n_ext = P.deep_count[p];
-    const uint32_t cnt = n_ext + P.deep_count[2 * kMaxParts + p];
-    uint32_t* next_ctr = P.deep_count + kMaxParts + p;
-    const uint32_t* dq = P.deep + (size_t)p * P.deep_cap;
-    const uint32_t* dqs = dq + P.part_cap - n_ext;   // dqs[idx] for idx >= n_ext
+    const DeepQueue Q = deep_queue(P, blockIdx.x % P.n_part);
 #ifdef XRT_EXPERIMENTS
-    if (blockIdx.x < P.n_part && tid == 0) atomicAdd(P.stats + 38, (unsigned long long)cnt);
+    if (blockIdx.x < P.n_part && tid == 0) atomicAdd(P.stats + 38, (unsigned long long)Q.cnt);
     uint32_t nsteps = 0, niter = 0;
 #endif
-    bool active = false, drained = cnt == 0, any = false;
-    uint32_t s = 0, l = 0;
-    int node = 0, sp = 0, bk = -1;
-    v3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
-    float tmax = 0.0f, bt = kINF, bu = 0.0f, bv = 0.0f;
+    DeepRay R;
+    R.drained = Q.cnt == 0;
     while (true) {
 #ifdef XRT_EXPERIMENTS
-        nsteps += active ? 1u : 0u;
+        nsteps += R.active ? 1u : 0u;
         ++niter;
 #endif
-        const uint64_t idle = __ballot(!active);
-        const uint32_t nidle = (uint32_t)__popcll(idle);
-        if (!drained && (nidle >= 16u || nidle == 64u)) {
-            const int leader = __ffsll((unsigned long long)idle) - 1;
-            uint32_t b = 0;
-            if (lane == leader) b = atomicAdd(next_ctr, nidle);
-            b = (uint32_t)__builtin_amdgcn_readlane((int)b, leader);
-            if (b + nidle >= cnt) drained = true;
-            if (!active) {
-                const uint32_t idx = b + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                if (idx < cnt) {
-                    const uint32_t e = idx < n_ext ? dq[idx] : dqs[idx];
-                    s = e >> 3;
-                    const uint32_t kind = e & 7u;
-                    any = kind != 0;
-                    if (!any) {
-                        o = xyz(P.ray_o[s]), d = xyz(P.ray_d[s]);
-                        const f4 h = P.hit[s];
-                        bt = h.x, bu = h.y, bv = h.z, bk = __float_as_int(h.w);
-                        tmax = kINF;
-                    } else {
-                        l = kind - 1u;
-                        const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                        o = xyz(a), tmax = a.w;
-                        d = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-                        bt = kINF, bk = -1;
-                    }
-                    inv = rcp3(d);
-                    node = 0, sp = 0;
-                    active = true;
-                }
-            }
-        }
-        if (!__ballot(active)) break;
-        if (!active) continue;
+        deep_fetch<1>(P, Q, R, lane);
+        if (!__ballot(R.active)) break;
+        if (!R.active) continue;
         f4 lo[4], hi[4];
         {
-            const f4* N = node < ntop ? top + 8 * node : P.bvh4 + 8 * (size_t)node;
+            const f4* N = R.node < ntop ? top + 8 * R.node : P.bvh4 + 8 * (size_t)R.node;
 #pragma unroll
             for (int c = 0; c < 4; ++c) lo[c] = N[c], hi[c] = N[4 + c];
         }
         float e[4];
         {
-            const float lim = any ? tmax : bt;
+            const float lim = R.any ? R.tmax : R.bt;
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                e[c] = __float_as_int(hi[c].w) >= 0 ? bvh_enter(lo[c], hi[c], o, inv, lim) : __builtin_inff();
+                e[c] = __float_as_int(hi[c].w) >= 0 ? bvh_enter(lo[c], hi[c], R.o, R.inv, lim) : __builtin_inff();
         }
         bool occluded = false;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {   // leaves first (either order gives the same result)
             const int k = __float_as_int(hi[c].w);
             if (!occluded && k > 0 && e[c] != __builtin_inff())
-                occluded = any ? bvh_leaf_batch<true>(P, __float_as_int(lo[c].w), k, o, d, tmax, bt, bu, bv, bk)
-                               : bvh_leaf_batch<false>(P, __float_as_int(lo[c].w), k, o, d, tmax, bt, bu, bv, bk);
+                occluded = R.any ? bvh_leaf_batch<true>(P, __float_as_int(lo[c].w), k, R.o, R.d, R.tmax, R.bt, R.bu, R.bv,
+                                                        R.bk)
+                                 : bvh_leaf_batch<false>(P, __float_as_int(lo[c].w), k, R.o, R.d, R.tmax, R.bt, R.bu, R.bv,
+                                                         R.bk);
         }
         bool done = occluded;
         if (!done) {
             // interior children still overlapping [0, lim] (bt may have shrunk at the leaves:
             // e <= bt is the same test as a fresh one against the smaller limit)
-            const float lim = any ? tmax : bt;
+            const float lim = R.any ? R.tmax : R.bt;
             int nx = -1;
             float en = __builtin_inff();
 #pragma unroll
@@ -436,20 +306,20 @@ __global__ __launch_bounds__(kBlock, XRT_DEEP_WAVES) void k_trace_deep4(KParams 
                 if (__float_as_int(hi[c].w) != 0 || !(e[c] <= lim)) continue;
                 const int idx = __float_as_int(lo[c].w);
                 if (nx < 0 || e[c] < en) {
-                    if (nx >= 0) stk[(sp++) * kBlock] = (SE)nx;
+                    if (nx >= 0) stk[(R.sp++) * kBlock] = (SE)nx;
                     nx = idx, en = e[c];
                 } else {
-                    stk[(sp++) * kBlock] = (SE)idx;
+                    stk[(R.sp++) * kBlock] = (SE)idx;
                 }
             }
-            if (nx >= 0) node = nx;
-            else if (sp == 0) done = true;
-            else node = (int)stk[(--sp) * kBlock];
+            if (nx >= 0) R.node = nx;
+            else if (R.sp == 0) done = true;
+            else R.node = (int)stk[(--R.sp) * kBlock];
         }
         if (done) {
-            if (!any) P.hit[s] = make_float4(bt, bu, bv, __int_as_float(bk));
-            else if (occluded) atomicOr(P.occ + s, 1u << l);
-            active = false;
+            if (!R.any) P.hit[R.s] = make_float4(R.bt, R.bu, R.bv, __int_as_float(R.bk));
+            else if (occluded) atomicOr(P.occ + R.s, 1u << R.l);
+            R.active = false;
         }
     }
 #ifdef XRT_EXPERIMENTS
@@ -472,91 +342,51 @@ __global__ __launch_bounds__(kBlock, XRT_DEEP_WAVES) void k_trace_deep4(KParams 
 // launch when few rays are queued (a row shard of a multi-GPU frame) — takes fewer cycles.
 // Exact for the same reason as k_trace_deep4: every triangle whose padded box overlaps
 // [0, best t] is tested by some lane (each lane's limit is at least the quad's best t).
-// Rays are fetched a quad at a time from the same partitioned queues and counters.
+// Rays are fetched a quad at a time from the same partitioned queues and counters (deep_fetch<4>:
+// when at least 4 quads are idle or all 16).
 template <typename SE>
 __global__ __launch_bounds__(kBlock, XRT_DEEP_WAVES) void k_trace_deep4q(KParams P) {
     extern __shared__ uint32_t bvh_stack_lds[];
     constexpr int kQuads = kBlock / 4;
     const int tid = threadIdx.x, lane = tid & 63, q = lane & 3;
-    const int ntop = P.bvh4_nodes < (int)kBvhTopNodes ? P.bvh4_nodes : (int)kBvhTopNodes;
-    f4* top = reinterpret_cast<f4*>(bvh_stack_lds);
-    for (int i = tid; i < 8 * ntop; i += kBlock) top[i] = P.bvh4[i];
-    SE* stk = reinterpret_cast<SE*>(bvh_stack_lds + 32 * ntop) + (tid >> 2);   // one stack per quad
+    const BvhLds B = bvh4_lds(P);
+    const f4* top = reinterpret_cast<const f4*>(bvh_stack_lds);
+    const int ntop = B.ntop;
+    SE* stk = bvh_top_load<SE>(bvh_stack_lds, P.bvh4, B, tid) + (tid >> 2);   // one stack per quad
     __syncthreads();
-    const uint32_t p = blockIdx.x % P.n_part;
-    // extension rays first, then shadow rays (queued apart by phase A), so a wave's lanes
-    // mostly run the same kind of walk (closest hit or any hit) at a time
-    const uint32_t n_ext = P.deep_count[p];
-    const uint32_t cnt = n_ext + P.deep_count[2 * kMaxParts + p];
-    uint32_t* next_ctr = P.deep_count + kMaxParts + p;
-    const uint32_t* dq = P.deep + (size_t)p * P.deep_cap;
-    const uint32_t* dqs = dq + P.part_cap - n_ext;   // dqs[idx] for idx >= n_ext
-    constexpr uint64_t kLeads = 0x1111111111111111ull;   // lane 0 of every quad
+    const DeepQueue Q = deep_queue(P, blockIdx.x % P.n_part);
 #ifdef XRT_EXPERIMENTS
-    if (blockIdx.x < P.n_part && tid == 0) atomicAdd(P.stats + 38, (unsigned long long)cnt);
+    constexpr uint64_t kLeads = 0x1111111111111111ull;   // lane 0 of every quad
+    if (blockIdx.x < P.n_part && tid == 0) atomicAdd(P.stats + 38, (unsigned long long)Q.cnt);
     uint32_t nsteps = 0, niter = 0;
 #endif
-    bool active = false, drained = cnt == 0, any = false;
-    uint32_t s = 0, l = 0;
-    int node = 0, sp = 0, bk = -1;
-    v3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
-    float tmax = 0.0f, bt = kINF, bu = 0.0f, bv = 0.0f;
+    DeepRay R;
+    R.drained = Q.cnt == 0;
     while (true) {
-        const uint64_t idle = __ballot(!active) & kLeads;
-        const uint32_t nidle = (uint32_t)__popcll(idle);
-        if (!drained && (nidle >= 4u || nidle == 16u)) {
-            const int leader = __ffsll((unsigned long long)idle) - 1;
-            uint32_t b = 0;
-            if (lane == leader) b = atomicAdd(next_ctr, nidle);
-            b = (uint32_t)__builtin_amdgcn_readlane((int)b, leader);
-            if (b + nidle >= cnt) drained = true;
-            if (!active) {
-                const uint32_t idx = b + (uint32_t)__popcll(idle & ((1ull << (lane & ~3)) - 1ull));
-                if (idx < cnt) {
-                    const uint32_t e = idx < n_ext ? dq[idx] : dqs[idx];
-                    s = e >> 3;
-                    const uint32_t kind = e & 7u;
-                    any = kind != 0;
-                    if (!any) {
-                        o = xyz(P.ray_o[s]), d = xyz(P.ray_d[s]);
-                        const f4 h = P.hit[s];
-                        bt = h.x, bu = h.y, bv = h.z, bk = __float_as_int(h.w);
-                        tmax = kINF;
-                    } else {
-                        l = kind - 1u;
-                        const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                        o = xyz(a), tmax = a.w;
-                        d = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-                        bt = kINF, bk = -1;
-                    }
-                    inv = rcp3(d);
-                    node = 0, sp = 0;
-                    active = true;
-                }
-            }
-        }
-        if (!__ballot(active)) break;
+        deep_fetch<4>(P, Q, R, lane);
+        if (!__ballot(R.active)) break;
 #ifdef XRT_EXPERIMENTS
         ++niter;
-        nsteps += (uint32_t)__popcll(__ballot(active) & kLeads);   // quads stepping (wave-uniform)
+        nsteps += (uint32_t)__popcll(__ballot(R.active) & kLeads);   // quads stepping (wave-uniform)
 #endif
-        if (!active) continue;
+        if (!R.active) continue;
         // ---- one node: child q on lane q; lim = the quad's best t (closest hits) or tmax
-        const f4* N = node < ntop ? top + 8 * node : P.bvh4 + 8 * (size_t)node;
+        const f4* N = R.node < ntop ? top + 8 * R.node : P.bvh4 + 8 * (size_t)R.node;
         const f4 lo = N[q], hi = N[4 + q];
         const int cidx = __float_as_int(lo.w), ccnt = __float_as_int(hi.w);
-        float lim = any ? tmax : __uint_as_float(group_min32<4>(__float_as_uint(bt)));   // t >= 0: bits order
-        const float e = ccnt >= 0 ? bvh_enter(lo, hi, o, inv, lim) : __builtin_inff();
+        float lim = R.any ? R.tmax : __uint_as_float(group_min32<4>(__float_as_uint(R.bt)));   // t >= 0: bits order
+        const float e = ccnt >= 0 ? bvh_enter(lo, hi, R.o, R.inv, lim) : __builtin_inff();
         bool done = false;
-        if (any) {
+        if (R.any) {
             bool occ = false;
-            if (ccnt > 0 && e != __builtin_inff()) occ = bvh_leaf_batch<true>(P, cidx, ccnt, o, d, tmax, bt, bu, bv, bk);
+            if (ccnt > 0 && e != __builtin_inff())
+                occ = bvh_leaf_batch<true>(P, cidx, ccnt, R.o, R.d, R.tmax, R.bt, R.bu, R.bv, R.bk);
             done = group_or32<4>(occ ? 1u : 0u) != 0u;
-            if (done && q == 0) atomicOr(P.occ + s, 1u << l);
+            if (done && q == 0) atomicOr(P.occ + R.s, 1u << R.l);
         } else {
             if (ccnt > 0 && e != __builtin_inff()) {
-                (void)bvh_leaf_batch<false>(P, cidx, ccnt, o, d, kINF, bt, bu, bv, bk);
-                lim = __builtin_fminf(lim, bt);   // this lane's leaf may have closed in
+                (void)bvh_leaf_batch<false>(P, cidx, ccnt, R.o, R.d, kINF, R.bt, R.bu, R.bv, R.bk);
+                lim = __builtin_fminf(lim, R.bt);   // this lane's leaf may have closed in
             }
             lim = __uint_as_float(group_min32<4>(__float_as_uint(lim)));
         }
@@ -567,23 +397,23 @@ __global__ __launch_bounds__(kBlock, XRT_DEEP_WAVES) void k_trace_deep4q(KParams
             if (nmin != ~0u) {
                 const bool nearest = nkey == nmin;
                 const uint32_t m4 = (uint32_t)(__ballot(inner && !nearest) >> (lane & ~3)) & 0xfu;
-                if (inner && !nearest) stk[(sp + __popc(m4 & ((1u << q) - 1u))) * kQuads] = (SE)cidx;
-                sp += __popc(m4);
-                node = (int)group_or32<4>(nearest ? (uint32_t)cidx : 0u);
-            } else if (sp == 0) {
+                if (inner && !nearest) stk[(R.sp + __popc(m4 & ((1u << q) - 1u))) * kQuads] = (SE)cidx;
+                R.sp += __popc(m4);
+                R.node = (int)group_or32<4>(nearest ? (uint32_t)cidx : 0u);
+            } else if (R.sp == 0) {
                 done = true;
             } else {
-                node = (int)stk[(--sp) * kQuads];
+                R.node = (int)stk[(--R.sp) * kQuads];
             }
         }
         if (done) {
-            if (!any) {   // the quad's closest hit: the smallest (t bits, index + 1) of the lanes
-                const uint64_t key = ((uint64_t)__float_as_uint(bt) << 32) | (uint32_t)(bk + 1);
+            if (!R.any) {   // the quad's closest hit: the smallest (t bits, index + 1) of the lanes
+                const uint64_t key = ((uint64_t)__float_as_uint(R.bt) << 32) | (uint32_t)(R.bk + 1);
                 const uint64_t kmin = group_min64<4>(key);
                 const uint32_t wm = (uint32_t)(__ballot(key == kmin) >> (lane & ~3)) & 0xfu;
-                if (q == __builtin_ctz(wm)) P.hit[s] = make_float4(bt, bu, bv, __int_as_float(bk));
+                if (q == __builtin_ctz(wm)) P.hit[R.s] = make_float4(R.bt, R.bu, R.bv, __int_as_float(R.bk));
             }
-            active = false;
+            R.active = false;
         }
     }
 #ifdef XRT_EXPERIMENTS
@@ -612,64 +442,40 @@ __global__ __launch_bounds__(kBlock) void k_trace_small(KParams P, const uint32_
     __syncthreads();
     const PartIter it = part_iter(P, count, kBlock);
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
-        const uint32_t i = base + tid;
-        const bool valid = i < it.n;
-        const uint32_t s = valid ? list[it.p * P.part_cap + i] : 0;
-        const uint32_t st = valid ? P.state[s] : 0;
-        const bool want = (st & ST_RAY) != 0;
-        const uint32_t smask = (st >> ST_SHADOW_SHIFT) & ((1u << NL) - 1u);
-        v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-        if (want) {
-            o = xyz(P.ray_o[s]);
-            d = xyz(P.ray_d[s]);
-        }
-        v3 so[NL], sd[NL];
-        float stmax[NL];
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-            so[l] = mk(0, 0, 0), sd[l] = mk(0, 0, 0), stmax[l] = 0.0f;
-            if (smask & (1u << l)) {
-                const f4 a = P.sh_o[(size_t)l * P.n_slots + s];
-                so[l] = xyz(a);
-                stmax[l] = a.w;
-                sd[l] = xyz(P.sh_d[(size_t)l * P.n_slots + s]);
-            }
-        }
-        const v3 inv = rcp3(d);
-        uint32_t occ = 0;
-        float best_t = kINF, bu = 0.0f, bv = 0.0f;
-        int best = -1;
+        const SlotRays<NL> R = load_slot_rays<NL>(P, list, it, base + tid);
+        const v3 inv = rcp3(R.d);
+        SlotHit H;
+        // small_scan<false, false> (trace_common.h) written out: through the helper this kernel's
+        // launches on the Cornell box at 128 spp took 0.7% longer than the parent's, beyond the
+        // parent's own spread in every repetition (profiles/trace_share_ab.json)
         for (int ob = 0; ob < P.n_objs; ++ob) {
             const DObjBox B = lbox[ob];
             const int cnt = B.count_occ & 0x7fffffff;
             const bool occluder = B.count_occ < 0;
-            const bool ne = want && box_overlap(o, inv, B, best_t);
+            const bool ne = R.want && box_overlap(R.o, inv, B, H.t);
             uint32_t nsm = 0;
             if (occluder) {
 #pragma unroll
                 for (int l = 0; l < NL; ++l)
-                    if ((smask & ~occ & (1u << l)) && box_overlap(so[l], rcp3(sd[l]), B, stmax[l])) nsm |= 1u << l;
+                    if ((R.smask & ~H.occ & (1u << l)) && box_overlap(R.so[l], rcp3(R.sd[l]), B, R.stmax[l])) nsm |= 1u << l;
             }
             if (__ballot(ne || nsm) == 0) continue;
             for (int k = B.first; k < B.first + cnt; ++k) {
                 const v3 v0 = xyz(ltri[3 * k]), e1 = xyz(ltri[3 * k + 1]), e2 = xyz(ltri[3 * k + 2]);
                 if (ne) {
                     float t, u, v;
-                    if (ray_tri(o, d, v0, e1, e2, t, u, v) && t < best_t) best_t = t, bu = u, bv = v, best = k;
+                    if (ray_tri(R.o, R.d, v0, e1, e2, t, u, v) && t < H.t) H.t = t, H.u = u, H.v = v, H.k = k;
                 }
 #pragma unroll
                 for (int l = 0; l < NL; ++l) {
-                    if (nsm & ~occ & (1u << l)) {
+                    if (nsm & ~H.occ & (1u << l)) {
                         float t, u, v;
-                        if (ray_tri(so[l], sd[l], v0, e1, e2, t, u, v) && t < stmax[l]) occ |= 1u << l;
+                        if (ray_tri(R.so[l], R.sd[l], v0, e1, e2, t, u, v) && t < R.stmax[l]) H.occ |= 1u << l;
                     }
                 }
             }
         }
-        if (valid) {
-            if (want) P.hit[s] = make_float4(best_t, bu, bv, __int_as_float(best));
-            if (smask) P.occ[s] = occ;
-        }
+        write_slot_hit(P, R, H);
     }
 }
 
@@ -681,19 +487,15 @@ hipError_t launch_trace_deep(const KParams& P, hipStream_t st) {
     if (!P.bvh4 || P.bvh4_stack <= 0 || P.bvh4_stack > kBvh4Stack) return hipErrorInvalidValue;
     const uint32_t db = P.n_part * std::max<uint32_t>(1u, std::min<uint32_t>(2048u / P.n_part,
                                                                             (P.deep_cap + kBlock - 1) / kBlock));
-    const bool small4 = P.bvh4_nodes <= 0x10000;
-    const size_t ntop4 = std::min<size_t>((size_t)P.bvh4_nodes, kBvhTopNodes);
-    const size_t lds4 = ntop4 * 8 * sizeof(f4) + (size_t)P.bvh4_stack * kBlock * (small4 ? sizeof(uint16_t) : sizeof(uint32_t));
-    if (P.deep_quad) {   // four lanes per ray: one stack per quad
-        const size_t lds4q = ntop4 * 8 * sizeof(f4) +
-                             (size_t)P.bvh4_stack * (kBlock / 4) * (small4 ? sizeof(uint16_t) : sizeof(uint32_t));
-        if (small4) hipLaunchKernelGGL((k_trace_deep4q<uint16_t>), dim3(db), dim3(kBlock), lds4q, st, P);
-        else hipLaunchKernelGGL((k_trace_deep4q<uint32_t>), dim3(db), dim3(kBlock), lds4q, st, P);
+    const BvhLds B = bvh4_lds(P);
+    return with_stack_entry(B, [&](auto se) {
+        using SE = decltype(se);
+        if (P.deep_quad)   // four lanes per ray: one stack per quad
+            hipLaunchKernelGGL((k_trace_deep4q<SE>), dim3(db), dim3(kBlock), B.bytes(P.bvh4_stack, kBlock / 4), st, P);
+        else
+            hipLaunchKernelGGL((k_trace_deep4<SE>), dim3(db), dim3(kBlock), B.bytes(P.bvh4_stack, kBlock), st, P);
         return hipGetLastError();
-    }
-    if (small4) hipLaunchKernelGGL((k_trace_deep4<uint16_t>), dim3(db), dim3(kBlock), lds4, st, P);
-    else hipLaunchKernelGGL((k_trace_deep4<uint32_t>), dim3(db), dim3(kBlock), lds4, st, P);
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_trace(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
@@ -703,11 +505,6 @@ hipError_t launch_trace(const KParams& P, const uint32_t* list, const uint32_t* 
         constexpr int NL = decltype(nl)::value;
         if (P.bvh_node && P.scene_kind == SCN_TRI) {
             if (P.bvh_stack <= 0 || P.bvh_stack > kBvhStack) return hipErrorInvalidValue;
-            // node indices below 2^16: 16-bit stack entries, half the LDS per thread
-            const bool small = P.bvh_nodes <= 0x10000;
-            const size_t ntop = std::min<size_t>((size_t)P.bvh_nodes, kBvhTopNodes);
-            const size_t lds =
-                ntop * 4 * sizeof(f4) + (size_t)P.bvh_stack * kBlock * (small ? sizeof(uint16_t) : sizeof(uint32_t));
             if (P.two_level) {
                 if (!P.deep || !P.deep_count) return hipErrorInvalidValue;
                 hipError_t e = zero_deep ? hipMemsetAsync(P.deep_count, 0, 3 * kMaxParts * sizeof(uint32_t), st)   // counts,
@@ -722,11 +519,12 @@ hipError_t launch_trace(const KParams& P, const uint32_t* list, const uint32_t* 
                 if (e == hipSuccess) e = hipGetLastError();
                 return e;   // phase B: launch_trace_deep
             }
-            if (small)
-                hipLaunchKernelGGL((k_trace_bvh<NL, uint16_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
-            else
-                hipLaunchKernelGGL((k_trace_bvh<NL, uint32_t>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, zero);
-            return hipGetLastError();
+            const BvhLds B = bvh_lds(P);
+            return with_stack_entry(B, [&](auto se) {
+                hipLaunchKernelGGL((k_trace_bvh<NL, decltype(se)>), dim3(blocks), dim3(kBlock), B.bytes(P.bvh_stack, kBlock),
+                                   st, P, list, count, zero);
+                return hipGetLastError();
+            });
         }
         if (P.small_tri) {
             const size_t lds = (size_t)P.n_tris * 3 * sizeof(f4) + (size_t)P.n_objs * sizeof(DObjBox);

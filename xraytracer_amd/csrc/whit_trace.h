@@ -3,8 +3,15 @@
 // (k_aov, k_aov_bvh).  A policy has three members — closest (Scene::intersect into a HitRec),
 // occluded (Scene::occluded) and surface (the hit's SurfaceInfo; returns the object index,
 // -1 = miss) — and `obj`, the object table that index goes into.
+//   WhitLds, whit_wave_off                   : a scene resident in LDS (k_whitted, k_aov)
+//   WhitBvhLayout, WhitBvh                   : a triangle scene beyond LDS through its BVH
+//   whit_bvh_setup, with_whit_bvh            : the block setup and the host dispatch of the two
+//                                              kernels over WhitBvh (k_whitted_bvh, k_aov_bvh)
+// The BVH's own share of LDS (top nodes, stack entry size) is bvh_walk.h's BvhLds.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "bvh_walk.h"
 #include "lds_stream.h"
@@ -39,14 +46,14 @@ struct WhitBvhLayout {
     uint32_t tri, box, plane, stack, wave, total;   // bytes; the top nodes are at 0
 };
 __host__ __device__ inline WhitBvhLayout whit_bvh_layout(const KParams& P) {
-    const uint32_t ntop = (uint32_t)P.bvh_nodes < kBvhTopNodes ? (uint32_t)P.bvh_nodes : kBvhTopNodes;
+    const BvhLds B = bvh_lds(P);
     const uint32_t nt = P.two_level ? (uint32_t)P.n_stri : 0u, ns = P.two_level ? (uint32_t)P.n_sobj : 0u;
     WhitBvhLayout L;
-    L.tri = 64u * ntop;
+    L.tri = B.stack();
     L.box = L.tri + 48u * nt;
     L.plane = L.box + (uint32_t)sizeof(DObjBox) * ns;
     L.stack = (L.plane + (uint32_t)sizeof(DObjPlane) * ns + 15u) & ~15u;
-    L.wave = (L.stack + (uint32_t)P.bvh_stack * kWhitBlock * (P.bvh_nodes <= 0x10000 ? 2u : 4u) + 15u) & ~15u;
+    L.wave = (L.stack + (uint32_t)P.bvh_stack * kWhitBlock * B.entry + 15u) & ~15u;
     L.total = L.wave + (kWhitBlock / 64) * kWhitWaveLds;
     return L;
 }
@@ -104,5 +111,41 @@ struct WhitBvh {
         return xrt::surface<SCN_TRI>(P, 0u, o, d, make_float4(h.t, h.u, h.v, __int_as_float(h.code)), S, t1);
     }
 };
+
+// The block's setup of k_whitted_bvh and k_aov_bvh over its dynamic LDS `lb`: carves the layout,
+// copies the top nodes and (TWO) the small objects in, syncs the block, and returns the policy
+// with the wave's slice (kWhitWaveLds: the stream, then the sum buffer).
+template <bool TWO, typename SE>
+struct WhitBvhBlock {
+    WhitBvh<TWO, SE> T;
+    uint32_t* st;
+};
+template <bool TWO, typename SE>
+__device__ __forceinline__ WhitBvhBlock<TWO, SE> whit_bvh_setup(const KParams& P, char* lb, int tid) {
+    const WhitBvhLayout Lo = whit_bvh_layout(P);
+    const BvhLds B = bvh_lds(P);
+    f4* ltri = reinterpret_cast<f4*>(lb + Lo.tri);
+    DObjBox* lbox = reinterpret_cast<DObjBox*>(lb + Lo.box);
+    DObjPlane* lpl = reinterpret_cast<DObjPlane*>(lb + Lo.plane);
+    (void)bvh_top_load<SE>(lb, P.bvh_node, B, tid, kWhitBlock);
+    if (TWO) {
+        lds_copy(ltri, P.stri, 3 * P.n_stri, tid, kWhitBlock);
+        lds_copy(lbox, P.sbox, P.n_sobj, tid, kWhitBlock);
+        lds_copy(lpl, P.splane, P.n_sobj, tid, kWhitBlock);
+    }
+    SE* stk = reinterpret_cast<SE*>(lb + Lo.stack) + tid;
+    uint32_t* st = reinterpret_cast<uint32_t*>(lb + Lo.wave + (tid >> 6) * kWhitWaveLds);
+    __syncthreads();
+    return {{P, reinterpret_cast<const f4*>(lb), B.ntop, stk, ltri, lbox, lpl, P.objs}, st};
+}
+
+// fn(std::bool_constant<TWO>{}, SE{}): the build of a WhitBvh kernel for this scene — two-level
+// or not, and the stack entry type its tree takes
+template <typename F>
+auto with_whit_bvh(const KParams& P, F&& fn) {
+    return with_stack_entry(bvh_lds(P), [&](auto se) {
+        return P.two_level ? fn(std::true_type{}, se) : fn(std::false_type{}, se);
+    });
+}
 
 }  // namespace xrt

@@ -299,25 +299,8 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
 template <bool TWO, typename SE>
 __global__ __launch_bounds__(kWhitBlock) void k_whitted_bvh(KParams P, uint32_t* __restrict__ work) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_whit_bvh[];
-    char* lb = reinterpret_cast<char*>(lds_whit_bvh);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const WhitBvhLayout Lo = whit_bvh_layout(P);
-    const int ntop = P.bvh_nodes < (int)kBvhTopNodes ? P.bvh_nodes : (int)kBvhTopNodes;
-    f4* top = lds_whit_bvh;
-    f4* ltri = reinterpret_cast<f4*>(lb + Lo.tri);
-    DObjBox* lbox = reinterpret_cast<DObjBox*>(lb + Lo.box);
-    DObjPlane* lpl = reinterpret_cast<DObjPlane*>(lb + Lo.plane);
-    lds_copy(top, P.bvh_node, 4 * ntop, tid, kWhitBlock);
-    if (TWO) {
-        lds_copy(ltri, P.stri, 3 * P.n_stri, tid, kWhitBlock);
-        lds_copy(lbox, P.sbox, P.n_sobj, tid, kWhitBlock);
-        lds_copy(lpl, P.splane, P.n_sobj, tid, kWhitBlock);
-    }
-    SE* stk = reinterpret_cast<SE*>(lb + Lo.stack) + tid;
-    uint32_t* st = reinterpret_cast<uint32_t*>(lb + Lo.wave + (tid >> 6) * kWhitWaveLds);
-    __syncthreads();
-    const WhitBvh<TWO, SE> T{P, top, ntop, stk, ltri, lbox, lpl, P.objs};
-    whit_pixels(P, T, st, work, lane);
+    const auto B = whit_bvh_setup<TWO, SE>(P, reinterpret_cast<char*>(lds_whit_bvh), threadIdx.x);
+    whit_pixels(P, B.T, B.st, work, threadIdx.x & 63);
 }
 
 // device self-test (xrt_test_whitted_math): the kernel's own geometry functions
@@ -347,30 +330,22 @@ bool use_whitted(const KParams& P) {
     return step_lds_bytes(P) != 0 && !P.two_level && whit_lds_bytes(P) <= kPixLds && whit_lds_bytes(P) <= P.lds_max;
 }
 
-template <int SCN>
-static hipError_t whitted_s(const KParams& P, uint32_t* work, hipStream_t st) {
-    const size_t lds = whit_lds_bytes(P);
-    auto kern = k_whitted<SCN>;
-    // persistent grid: as many blocks as fit on the device at once, at most one wave per pixel
-    int dev = 0, ncu = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWhitBlock, lds);
+// one launch of a Whitted kernel over the shard's pixels: a persistent grid, at most one wave per pixel
+template <typename K>
+static hipError_t whit_launch(K kern, size_t lds, const KParams& P, uint32_t* work, hipStream_t st) {
+    uint32_t blocks = 0;
+    const hipError_t e = persistent_blocks(kern, kWhitBlock, lds, P.n_slots, &blocks);
     if (e != hipSuccess) return e;
-    const uint64_t want = ((uint64_t)P.n_slots + kWhitBlock / 64 - 1) / (kWhitBlock / 64);
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(kWhitBlock), lds, st, P, work);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWhitBlock), lds, st, P, work);
     return hipGetLastError();
 }
 
 hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st) {
     if (!use_whitted(P)) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
-    switch (P.scene_kind) {
-        case SCN_TRI: return whitted_s<SCN_TRI>(P, work, st);
-        case SCN_SPHERE: return whitted_s<SCN_SPHERE>(P, work, st);
-        default: return whitted_s<SCN_MIXED>(P, work, st);
-    }
+    return with_scene_kind(P.scene_kind, [&](auto scn) {
+        return whit_launch(k_whitted<decltype(scn)::value>, whit_lds_bytes(P), P, work, st);
+    });
 }
 
 size_t whit_bvh_lds_bytes(const KParams& P) { return whit_bvh_layout(P).total; }
@@ -384,28 +359,12 @@ bool use_whitted_bvh(const KParams& P) {
            whit_bvh_lds_bytes(P) <= kPixLds && whit_bvh_lds_bytes(P) <= P.lds_max;
 }
 
-template <bool TWO, typename SE>
-static hipError_t whitted_bvh_s(const KParams& P, uint32_t* work, hipStream_t st) {
-    const size_t lds = whit_bvh_lds_bytes(P);
-    auto kern = k_whitted_bvh<TWO, SE>;
-    // persistent grid, as whitted_s
-    int dev = 0, ncu = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWhitBlock, lds);
-    if (e != hipSuccess) return e;
-    const uint64_t want = ((uint64_t)P.n_slots + kWhitBlock / 64 - 1) / (kWhitBlock / 64);
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, per_cu) * ncu, want));
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(kWhitBlock), lds, st, P, work);
-    return hipGetLastError();
-}
-
 hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st) {
     if (!use_whitted_bvh(P)) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
-    const bool small = P.bvh_nodes <= 0x10000;   // node indices below 2^16: 16-bit stack entries
-    if (P.two_level) return small ? whitted_bvh_s<true, uint16_t>(P, work, st) : whitted_bvh_s<true, uint32_t>(P, work, st);
-    return small ? whitted_bvh_s<false, uint16_t>(P, work, st) : whitted_bvh_s<false, uint32_t>(P, work, st);
+    return with_whit_bvh(P, [&](auto two, auto se) {
+        return whit_launch(k_whitted_bvh<decltype(two)::value, decltype(se)>, whit_bvh_lds_bytes(P), P, work, st);
+    });
 }
 
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st) {
