@@ -215,7 +215,10 @@ struct RenderPlan {
     // k_step_spec in the merged schedule's group layouts, which needs the camera lists.
     // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it, or
     // (whitted_bvh) k_whitted_bvh for a scene beyond LDS under XRT_FLAG_WHITTED_BVH
-    bool pixel, fused, merged, two_level, step_tri, spec, camlist, whitted, whitted_bvh;
+    // elide: GI in the merged schedule over at most 64 triangles — k_camlist runs right after the
+    // seeding refill, with or without speculative launches, and finishes the pixels no camera
+    // ray can hit (spec.hip)
+    bool pixel, fused, merged, two_level, step_tri, spec, camlist, elide, whitted, whitted_bvh;
     uint32_t n_part, part_cap;                     // live-list partitions
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
@@ -240,12 +243,16 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p) {
     R.step_tri = R.fused && !R.merged && use_step_tri(P);
     R.spec = R.merged && !R.two_level && !(p->flags & XRT_FLAG_NO_SPEC) && use_step_spec(P);
     R.camlist = R.spec && !exp_env("XRT_NO_CAMLIST");
+    // Direct (under XRT_FLAG_NO_PIXEL) keeps tracing its empty pixels: its miss adds the
+    // background per sample, an in-order float sum with no closed form
+    R.elide = XRT_CAM_ELIDE && !exp_env("XRT_NO_ELIDE") && R.merged && !R.two_level && !R.pixel &&
+              p->integrator == XRT_INTEGRATOR_GI && p->max_depth >= 1 && p->spp >= 1 && P.n_tris <= 64;
     // WhittedIntegrator has one schedule, whatever the schedule flags say (render_impl has
     // refused the scenes it cannot hold): one wave per pixel, one lane per sample (whitted.hip),
     // over the LDS scene when it fits, else — XRT_FLAG_WHITTED_BVH — through the triangle BVH
     R.whitted = p->integrator == XRT_INTEGRATOR_WHITTED;
     R.whitted_bvh = R.whitted && (p->flags & XRT_FLAG_WHITTED_BVH) && !use_whitted(P) && use_whitted_bvh(P);
-    if (R.whitted) R.pixel = true, R.two_level = R.merged = R.step_tri = R.spec = R.camlist = false;
+    if (R.whitted) R.pixel = true, R.two_level = R.merged = R.step_tri = R.spec = R.camlist = R.elide = false;
     R.schedule = R.whitted_bvh ? XRT_SCHED_WHITTED_BVH
                  : R.whitted   ? XRT_SCHED_WHITTED
                  : R.pixel     ? XRT_SCHED_PIXEL
@@ -363,6 +370,9 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
             return R.merged ? launch_refill_merged(P, L.req(0), L.req(1), c->stream)
                             : launch_refill(P, L.req(0), L.req(1), c->stream);
         }));
+        // the camera lists now, not before the first speculative launch: the pixels they prove
+        // empty are finished before any step launch loads them
+        if (R.elide) HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_camlist(P, true, c->stream); }));
     }
     HIPCHK(c, hipMemcpyAsync(c->kparams.p, &P, sizeof(KParams), hipMemcpyHostToDevice, c->stream));
     return XRT_OK;
@@ -379,7 +389,8 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
               uint64_t& it) {
     const KParams* dP = as<KParams>(c->kparams);
     const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // k_step, k_step_tri: one entry per thread
-    bool camlist_pending = R.camlist;   // built before the first launch that reads them, timed with the seeding
+    // built before the first launch that reads them (seed_paths has when it elides), timed with the seeding
+    bool camlist_pending = R.camlist && !R.elide;
     for (it = 0; it < R.cap_iters && !poll.done; ++it) {
         const uint32_t *list = L.list[it & 1], *ci = L.counts(it % 3);
         uint32_t *out = L.list[~it & 1], *co = L.counts((it + 1) % 3), *cz = L.counts((it + 2) % 3);
@@ -392,7 +403,7 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
         if (spec_now) T.S.spec_launches++;
         if (spec_now && camlist_pending) {
             camlist_pending = false;
-            HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_camlist(P, c->stream); }));
+            HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_camlist(P, false, c->stream); }));
         }
         const hipError_t e = T.launch(XRT_K_STEP, [&] {
             if (spec_now)

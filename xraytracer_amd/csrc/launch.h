@@ -124,12 +124,13 @@ hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObj
 
 // ----------------------------------------------------------------------- spec.hip ----
 // speculative sample starts for the merged schedule's group layouts: eligibility,
-// the per-slot camera lists (once per render, before the first speculative launch), and the
-// step launch at spw = 16, 8 or 4 slots per wave (same list / counter contract as
-// launch_step_merged)
+// the per-slot camera lists (once per render, before the first speculative launch; with
+// `retire`, right after the seeding refill, and the pixels whose list is empty are finished
+// there: it then runs whether or not P.camlist is set), and the step launch at spw = 16, 8 or
+// 4 slots per wave (same list / counter contract as launch_step_merged)
 bool use_step_spec(const KParams& P);
 constexpr uint32_t kSpecDraws = 11;   // stream words one k_step_spec visit may read past the cursor
-hipError_t launch_camlist(const KParams& P, hipStream_t st);
+hipError_t launch_camlist(const KParams& P, bool retire, hipStream_t st);
 hipError_t launch_step_spec(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count,
                             uint32_t* out, uint32_t* out_count, uint32_t* zero, uint32_t visits, uint32_t part_live,
                             uint32_t spw, hipStream_t st);

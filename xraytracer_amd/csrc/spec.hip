@@ -76,7 +76,16 @@ __device__ __forceinline__ v3 qsel3(v3 v, int src_lane) {
 // larger on every ray of the cone, so it is never the (t, index) minimum.  When one triangle
 // is left and it covers the cone, every camera ray of the pixel hits it: `covering` is then
 // its index and the candidate rays need no test (the shading recomputes t, u, v anyway).
-__global__ __launch_bounds__(kBlock) void k_camlist(KParams P) {
+//
+// retire (plan_render's elide: GIIntegrator, XRT_CAM_ELIDE): a pixel whose set is empty before
+// the covering cull — which cannot empty a set: the covering triangle stays — is finished here.
+// Each of its spp samples draws its two jitter words, calls Scene::intersect once, misses and
+// adds (0 + 1 * 0) / 1 = +0, which addPixel accepts (Src/integrator.h:214-221,
+// Src/renderer.cpp:44-75); x + 0 spp times is x + 0 once (-0 becomes +0, NaN stays NaN).  So the
+// slot gets the state the path would have ended in (c_shadow and c_rej stay k_seed's 0, rng_g
+// the seeding refill's) and the step kernels, which load it as ST_DONE, drop it from the live
+// list in their first launch.
+__global__ __launch_bounds__(kBlock) void k_camlist(KParams P, uint32_t retire) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= P.n_slots) return;
     const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
@@ -145,6 +154,15 @@ __global__ __launch_bounds__(kBlock) void k_camlist(KParams P) {
         }
         if (cov) cover |= 1ull << t;
     }
+    if (retire && mask == 0) {
+        P.state[s] = ST_DONE;
+        P.sample_k[s] = P.spp;
+        P.c_seg[s] = P.spp;
+        P.rng_c[s] = kMT + 2u * P.spp;
+        float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
+        px[0] = px[0] + 0.0f, px[1] = px[1] + 0.0f, px[2] = px[2] + 0.0f;
+    }
+    if (!P.camlist) return;   // no speculative launches (plan_render): the lists have no reader
     // a covering triangle hides the triangles wholly beyond its plane (as seen from o)
     uint64_t keep = mask;
     for (uint64_t cb = cover; cb; cb &= cb - 1ull) {
@@ -550,8 +568,8 @@ bool use_step_spec(const KParams& P) {
            P.n_tris <= 64 && !(P.rflags & XRT_FLAG_NO_GROUP) && use_step_merged(P);
 }
 
-hipError_t launch_camlist(const KParams& P, hipStream_t st) {
-    hipLaunchKernelGGL(k_camlist, dim3((P.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, P);
+hipError_t launch_camlist(const KParams& P, bool retire, hipStream_t st) {
+    hipLaunchKernelGGL(k_camlist, dim3((P.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, P, retire ? 1u : 0u);
     return hipGetLastError();
 }
 

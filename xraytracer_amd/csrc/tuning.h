@@ -119,6 +119,9 @@
 #ifndef XRT_SPEC_TAIL
 #define XRT_SPEC_TAIL 1      // speculative starts in the 4-slot tail launches too (k_step_spec<4, 16>)
 #endif
+#ifndef XRT_CAM_ELIDE
+#define XRT_CAM_ELIDE 1      // GI, merged schedule: pixels no camera ray can hit are finished by k_camlist (C2: 45.6% of them)
+#endif
 
 // ---- experiment builds
 #ifndef XRT_PHASE_CLOCK
