@@ -3,8 +3,6 @@
 cases and the situations they are chosen for are in tests/aov_restatement.py and checked without
 a GPU in tests/test_aov_restatement.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,28 +11,16 @@ import aov_restatement as ar
 import multi_stats
 import pyoracle
 import whitted_bvh_scenes as wb
+from gpu_checks import assert_same_bits, read_ppm, render_rc, run_example, words
 from xraytracer_amd import abi
 from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.int32).view(np.uint32)
-
-
-def first_diff(a, b):
-    d = np.argwhere(words(a) != words(b))
-    return [(tuple(int(x) for x in q), a[tuple(q)].item(), b[tuple(q)].item()) for q in d[:4]]
-
 
 def assert_planes(got, ref, names=ar.PLANES):
     for k in names:
-        assert got[k].dtype == ref[k].dtype and got[k].shape == ref[k].shape, k
-        assert np.array_equal(words(got[k]), words(ref[k])), (k, first_diff(got[k], ref[k]))
+        assert_same_bits(got[k], ref[k], k)
 
 
 def check_case(name, devices=None, want_kernel=None):
@@ -66,15 +52,8 @@ def test_bvh_scenes(name):
     check_case("bvh_" + name)
     # the same scene is refused by a Whitted render without XRT_FLAG_WHITTED_BVH: the guide pass
     # took the BVH kernel by itself
-    s = ar.scene("bvh_" + name)
-    r = HipRenderer(1)
-    try:
-        r.upload(s)
-        p = r.params(s, 24, 18, integrator="whitted")
-        img = np.zeros((18, 24, 3), np.float32)
-        assert abi.lib().xrt_render(r.ctx, C.byref(p), abi.fptr(img), None) == abi.XRT_ERR_UNSUPPORTED
-    finally:
-        r.close()
+    rc, _ = render_rc(ar.scene("bvh_" + name), 24, 18, 1, integrator="whitted")
+    assert rc == abi.XRT_ERR_UNSUPPORTED
 
 
 # 3. the ordered sum across windows, runs of the sum buffer and ring chunks
@@ -280,14 +259,8 @@ def test_aov_example_ppm(tmp_path):
     _, w, h, spp, _ = ar.CASES["example"]
     ref, _, _ = ar.reference("example")
     prefix = tmp_path / "guides"
-    subprocess.run([os.path.join(ROOT, "examples", "bin", "aov"), str(w), str(h), str(spp), str(prefix)], check=True,
-                   capture_output=True, text=True)
-
-    def ppm(path):
-        tok = path.read_text().split()
-        assert tok[:4] == ["P3", str(w), str(h), "255"]
-        return np.array(tok[4:], np.int64).reshape(h, w, 3)
-
+    run_example("aov", w, h, spp, prefix)
     half = np.float32(0.5) * (ref["normal"] + np.float32(1.0))   # 0.5f * (ns + 1.0f)
-    assert np.array_equal(ppm(tmp_path / "guides.normal.ppm"), pyoracle.tonemap(half, 1.2).astype(np.int64))
-    assert np.array_equal(ppm(tmp_path / "guides.albedo.ppm"), pyoracle.tonemap(ref["albedo"], 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "guides.normal.ppm", w, h), pyoracle.tonemap(half, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "guides.albedo.ppm", w, h),
+                          pyoracle.tonemap(ref["albedo"], 1.2).astype(np.int64))

@@ -14,38 +14,15 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, counters_equal, render_pair, renderer  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-RMSE_TOL = 1e-3  # BASELINE.json north_star: per-channel RMSE < 1e-3 at matched seeds
-
-
-def compare(img, ref):
-    assert img.shape == ref.shape
-    rmse = np.sqrt(np.mean((img.astype(np.float64) - ref.astype(np.float64)) ** 2, axis=(0, 1)))
-    assert np.all(rmse < RMSE_TOL), rmse
-    bad = np.argwhere(~np.all(img == ref, axis=-1))
-    assert len(bad) == 0, (len(bad), bad[:5], rmse)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(1, device=0)
-    yield r
-    r.close()
-
 
 def render_both(r, scene, w, h, spp, **kw):
-    r.spp = spp
-    r._uploaded = None
-    img = r.render(scene, w, h, **kw)
-    okw = {k: v for k, v in kw.items() if k in ("integrator", "max_depth", "shard_index", "shard_count")}
-    ref, st = pyoracle.render(scene, w, h, spp, **okw)
-    g = r.stats
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected) == \
-        (st["segments"], st["shadow_rays"], st["draws"], st["rejected"])
+    img, ref, st, g = render_pair(r, scene, w, h, spp, **kw)
+    counters_equal(g, st, ("segments", "shadow_rays", "draws", "rejected"))
     return img, ref, st
 
 
@@ -70,7 +47,7 @@ def sphere_field(w, h, area=True):
 def test_direct_area_sphere_light(renderer, schedule, expect):
     s = sphere_field(96, 64)
     img, ref, st = render_both(renderer, s, 96, 64, 24, schedule=schedule)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.schedule == expect
     assert st["shadow_rays"] > 0
     # the two samplings draw the same words but place the light samples differently
@@ -82,7 +59,7 @@ def test_direct_area_sphere_light(renderer, schedule, expect):
 def test_gi_area_sphere_light(renderer, schedule, expect):
     s = sphere_field(64, 48)
     img, ref, st = render_both(renderer, s, 64, 48, 8, integrator="gi", max_depth=3, schedule=schedule)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.schedule == expect
     assert st["segments"] > 64 * 48 * 8
 
@@ -103,7 +80,7 @@ def cornell_area_sphere_light(w, h):
 def test_cornell_gi_area_sphere_light(renderer, schedule):
     s = cornell_area_sphere_light(48, 36)
     img, ref, st = render_both(renderer, s, 48, 36, 8, schedule=schedule)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_vpt_nee_area_sphere_light(renderer):
@@ -120,5 +97,5 @@ def test_vpt_nee_area_sphere_light(renderer):
     s.camera = scenes.pinhole((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, c, c, c + 2.2 * n, 1), 45.0, 24, 18)
     s.integrator, s.max_depth = "vpt_nee", 10
     img, ref, st = render_both(renderer, s, 24, 18, 6)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert st["shadow_rays"] > 0

@@ -15,20 +15,10 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, counters_equal, render_pair, renderer  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
-
-RMSE_TOL = 1e-3  # BASELINE.json north_star: per-channel RMSE < 1e-3 at matched seeds
-
-
-def compare(img, ref):
-    assert img.shape == ref.shape
-    rmse = np.sqrt(np.mean((img.astype(np.float64) - ref.astype(np.float64)) ** 2, axis=(0, 1)))
-    assert np.all(rmse < RMSE_TOL), rmse
-    bad = np.argwhere(~np.all(img == ref, axis=-1))
-    assert len(bad) == 0, (len(bad), bad[:5], rmse)
 
 
 def partitions(n_slots, merged=False):
@@ -37,18 +27,6 @@ def partitions(n_slots, merged=False):
     max_parts, min_slots = (256, 2048) if merged else (1024, 512)
     n = min(max_parts, max(1, n_slots // min_slots))
     return n & ~7 if n >= 8 else n
-
-
-def counters_equal(g, st):
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected, g.stalled) == \
-        (st["segments"], st["shadow_rays"], st["draws"], st["rejected"], st["stalled"])
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(1, device=0)
-    yield r
-    r.close()
 
 
 def render_like_bench(r, cfg, spp, schedule="auto"):
@@ -77,7 +55,7 @@ def test_c2_headline_geometry(renderer):
     assert g.schedule == abi.XRT_SCHED_STEP_MERGED
     assert (g.slots_per_wave, g.group_lanes, g.partitions, g.visits_per_launch) == (64, 1, partitions(480000, merged=True), 64)
     assert g.samples == 800 * 600 * 4
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -96,7 +74,7 @@ def test_c2_headline_across_launches(renderer):
     # in-launch refills ran (measured: 258,950 for 480,000 slots — pixels whose samples end
     # after one segment draw ~2.5 words per sample and never run low)
     assert g.rng_twists - g.path_slots > g.path_slots // 4, (g.rng_twists, g.path_slots)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -125,7 +103,7 @@ def test_c3_geometry_across_launches(renderer):
     assert g.segments == w * h * spp   # Direct: one Scene::intersect per sample
     k, n = 21, 64
     ref, st = pyoracle.render(scene, w, h, spp, shard_index=k, shard_count=n)
-    compare(img[k::n], ref[k::n])
+    assert_frame(img[k::n], ref[k::n])
 
 
 def test_c3_row_shard(renderer):
@@ -150,7 +128,7 @@ def test_c3_row_shard(renderer):
     owned[3::8] = True
     assert np.all(img[~owned] == 0)
     ref, _ = pyoracle.render(scene, w, h, spp, shard_index=3, shard_count=64)
-    compare(img[3::64], ref[3::64])
+    assert_frame(img[3::64], ref[3::64])
 
 
 @pytest.mark.parametrize("schedule", ["auto", "step"])
@@ -161,7 +139,7 @@ def test_c3_geometry(renderer, schedule):
     img, ref, st, g = render_like_bench(renderer, "C3", 1, schedule=schedule)
     assert g.schedule == (abi.XRT_SCHED_PIXEL if schedule == "auto" else abi.XRT_SCHED_STEP)
     assert g.partitions == partitions(1280 * 720)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -175,18 +153,14 @@ def test_c4_mesh_geometry(renderer, sched, deep):
     one (XRT_FLAG_DEEP_SINGLE)."""
     s = scenes.cornell_spheremesh(160, 90)
     assert s.desc.n_tris == 51200 + 36
-    renderer.spp = 2
-    renderer.upload(s)
-    img = renderer.render(s, 160, 90, timing=True, deep=deep, schedule=sched)
-    g = renderer.stats
+    img, ref, st, g = render_pair(renderer, s, 160, 90, 2, timing=True, deep=deep, schedule=sched)
     if sched == "auto":
         assert g.schedule == abi.XRT_SCHED_STEP_BVH and g.launches[abi.XRT_K_STEP] > 0
         assert g.launches[abi.XRT_K_TRACE] == g.launches[abi.XRT_K_DEEP] == g.launches[abi.XRT_K_SHADE] == 0
     else:
         assert g.schedule == abi.XRT_SCHED_WAVEFRONT and g.launches[abi.XRT_K_STEP] == 0
         assert g.launches[abi.XRT_K_DEEP] == g.launches[abi.XRT_K_TRACE] > 0
-    ref, st = pyoracle.render(s, 160, 90, 2)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -228,7 +202,7 @@ def test_c4_full_geometry(renderer):
     assert g.launches[abi.XRT_K_STEP] >= 2 and g.layout_launches[0] >= 1   # full waves first
     ref, _ = c4_reference()
     k, n = C4_SUB
-    compare(img[k::n], ref[k::n])
+    assert_frame(img[k::n], ref[k::n])
 
 
 def test_c4_row_shard(renderer):
@@ -244,7 +218,7 @@ def test_c4_row_shard(renderer):
     assert np.all(img[~owned] == 0)
     ref, _ = c4_reference()
     k, n = C4_SUB
-    compare(img[k::n], ref[k::n])
+    assert_frame(img[k::n], ref[k::n])
 
 
 C4_TWIST_SPP = 96
@@ -280,13 +254,13 @@ def test_c4_kernel_twists_in_launch(renderer, spw, shard):
     if spw:
         assert g.layout_launches[abi.LAYOUTS.index(spw)] == g.launches[abi.XRT_K_STEP]
     if shard is None:
-        compare(img, ref)
+        assert_frame(img, ref)
         counters_equal(g, st)
     else:
         owned = np.zeros(36, bool)
         owned[shard::8] = True
         assert np.all(img[~owned] == 0)
-        compare(img[owned], ref[owned])
+        assert_frame(img[owned], ref[owned])
 
 
 def test_c5_full_frame(renderer):
@@ -298,7 +272,7 @@ def test_c5_full_frame(renderer):
     assert g.schedule == abi.XRT_SCHED_STEP
     assert g.partitions == partitions(800 * 600) == 936
     assert g.launches[abi.XRT_K_STEP] >= 2, list(g.launches)   # 128 events per launch: walks carried over
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert st["segments"] > 0
 
@@ -308,13 +282,9 @@ def test_c5_grid_geometry(renderer):
     4:3 aspect (200x150, 8 spp) — fused k_step<VPT> with walks that suspend across refills."""
     s = scenes.smoke(200, 150)
     assert s.medium.density.shape == (128, 128, 128)
-    renderer.spp = 8
-    renderer.upload(s)
-    img = renderer.render(s, 200, 150, timing=True)
-    g = renderer.stats
+    img, ref, st, g = render_pair(renderer, s, 200, 150, 8, timing=True)
     assert g.schedule == abi.XRT_SCHED_STEP
-    ref, st = pyoracle.render(s, 200, 150, 8)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert st["segments"] > 0 and st["draws"] > 8 * 200 * 150 * 2
 
@@ -338,11 +308,11 @@ def test_render_device_repeated_steps_ordered_after_caller_stream(renderer):
             junk = junk / junk.norm()
         fb.add_(1000.0 + junk[0, 0])
         renderer.render_device(s, 160, 120, fb.data_ptr(), after_stream=torch.cuda.current_stream().cuda_stream)
-        compare(fb.cpu().numpy(), ref)
+        assert_frame(fb.cpu().numpy(), ref)
     # the device-wide form (no stream given) orders the same way
     fb.fill_(5.0)
     renderer.render_device(s, 160, 120, fb.data_ptr())
-    compare(fb.cpu().numpy(), ref)
+    assert_frame(fb.cpu().numpy(), ref)
 
 
 @pytest.mark.parametrize("schedule", ["auto", "wavefront"])
@@ -354,22 +324,19 @@ def test_accumulates_into_a_nonzero_image(renderer, schedule):
     s = scenes.cornell(64, 48)
     rng = np.random.default_rng(5)
     init = rng.uniform(0.0, 3.0, (48, 64, 3)).astype(np.float32)
-    renderer.spp = 4
-    renderer.upload(s)
-    img = renderer.render(s, 64, 48, initial=init, schedule=schedule)
-    ref, st = pyoracle.render(s, 64, 48, 4, initial=init)
-    compare(img, ref)
+    img, ref, _, _ = render_pair(renderer, s, 64, 48, 4, initial=init, schedule=schedule)
+    assert_frame(img, ref)
     plain, _ = pyoracle.render(s, 64, 48, 4)
     assert not np.array_equal(ref, plain)
     fb = torch.from_numpy(init).to("cuda:0")
     renderer.render_device(s, 64, 48, fb.data_ptr(), accumulate=True, schedule=schedule)
-    compare(fb.cpu().numpy(), ref)
+    assert_frame(fb.cpu().numpy(), ref)
     # a shard accumulates its own rows and leaves the others as they were
     fb = torch.from_numpy(init).to("cuda:0")
     renderer.render_device(s, 64, 48, fb.data_ptr(), accumulate=True, shard_index=1, shard_count=2,
                            schedule=schedule)
     out = fb.cpu().numpy()
-    compare(out[1::2], ref[1::2])
+    assert_frame(out[1::2], ref[1::2])
     assert np.array_equal(out[0::2], init[0::2])
 
 
@@ -388,7 +355,7 @@ def test_rejected_samples(renderer, schedule):
     for integ in ("gi", "direct"):
         img = renderer.render(s, 64, 48, integrator=integ, schedule=schedule)
         ref, st = pyoracle.render(s, 64, 48, 6, integrator=integ)
-        compare(img, ref)
+        assert_frame(img, ref)
         assert st["rejected"] > 1000
         counters_equal(renderer.stats, st)
 

@@ -3,25 +3,16 @@ Src/examples/vpt.cpp:20-83, examples/nee.cpp ← Src/examples/nee.cpp:20-82), re
 HipRenderer through HipRenderer::render's medium branches (csrc/host/hip_renderer.cpp) and
 compared bit for bit with the oracle on the same scene built through the Python layer.
 """
-import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, run_example
 from xraytracer_amd import scenes
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def run(exe, args):
-    return subprocess.run([os.path.join(ROOT, "examples", "bin", exe)] + [str(a) for a in args], check=True,
-                          capture_output=True, text=True).stdout
 
 
 def test_vpt_example_homogeneous_mis(tmp_path):
@@ -29,7 +20,7 @@ def test_vpt_example_homogeneous_mis(tmp_path):
     FOV = 2 * 180 * atanf(1/3) / PI."""
     w, h, spp = 64, 64, 8
     out = tmp_path / "vpt.raw"
-    log = run("vpt", [w, h, spp, out])
+    log = run_example("vpt", w, h, spp, out)
     img = np.fromfile(out, dtype=np.float32).reshape(h, w, 3)
     fov = float.fromhex(re.search(r"FOV (\S+)", log).group(1))
     # GCC folds atanf(1.0f / 3.0f) at compile time: the correctly rounded value
@@ -44,7 +35,7 @@ def test_vpt_example_homogeneous_mis(tmp_path):
     s.integrator, s.max_depth = "vpt", 10
     ref, st = pyoracle.render(s, w, h, spp)
     assert st["segments"] > w * h * spp
-    assert np.array_equal(img, ref), np.argwhere(~np.all(img == ref, axis=-1))[:5]
+    assert_frame(img, ref)
 
 
 @pytest.mark.parametrize("layout", ["dense", "sparse"])
@@ -58,7 +49,7 @@ def test_nee_example_heterogeneous_dense_grid(tmp_path, layout):
     gpath = tmp_path / "grid.raw"
     np.ascontiguousarray(grid, dtype=np.float32).tofile(gpath)
     out = tmp_path / "nee.raw"
-    run("nee", [gpath, n, n, n, *origin, voxel, w, h, spp, out, layout])
+    run_example("nee", gpath, n, n, n, *origin, voxel, w, h, spp, out, layout)
     img = np.fromfile(out, dtype=np.float32).reshape(h, w, 3)
     s = scenes.SceneBundle()
     s.add_medium("medium", scenes.Medium(grid, origin, voxel, 0.0, (0.01, 0.01, 0.01), (0.05, 0.05, 0.05)))
@@ -68,4 +59,4 @@ def test_nee_example_heterogeneous_dense_grid(tmp_path, layout):
     s.integrator, s.max_depth = "vpt_nee", 32
     ref, st = pyoracle.render(s, w, h, spp)
     assert st["shadow_rays"] > 0 and st["segments"] > 0
-    assert np.array_equal(img, ref), np.argwhere(~np.all(img == ref, axis=-1))[:5]
+    assert_frame(img, ref)

@@ -3,8 +3,6 @@
 XRT_DENOISE_NO_TILE.  The cases and the situations they are chosen for are in
 tests/denoise_restatement.py and checked without a GPU in tests/test_denoise_restatement.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,29 +10,12 @@ import pytest
 import aov_restatement as ar
 import denoise_restatement as dr
 import pyoracle
+from gpu_checks import assert_same_bits, read_ppm, run_example, words
+from gpu_checks import renderer as r  # noqa: F401 -- the shared fixture, under the name the tests here ask for
 from xraytracer_amd import abi, scenes
 from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def words(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_same(got, ref):
-    assert got.shape == ref.shape and got.dtype == np.float32
-    d = np.argwhere(words(got) != words(ref))
-    assert len(d) == 0, (len(d), [(tuple(int(x) for x in q), got[tuple(q)].item(), ref[tuple(q)].item()) for q in d[:4]])
-
-
-@pytest.fixture(scope="module")
-def r():
-    h = HipRenderer(1)
-    yield h
-    h.close()
 
 
 def check_stats(st, iterations, tile):
@@ -51,7 +32,7 @@ def test_cases(r, name, tile):
     kw = dr.CASES[name][3]
     got = r.denoise(color, g, tile=tile, **kw)
     check_stats(r.denoise_stats, kw["iterations"], tile)
-    assert_same(got, dr.reference(name)[0])
+    assert_same_bits(got, dr.reference(name)[0])
 
 
 # 2. guide-plane subsets: a plane left out is a plane of zeros
@@ -62,13 +43,13 @@ def test_plane_subsets(r, subset):
     sub = {k: g[k] for k in subset}
     ref = dr.denoise(color, sub, **kw)
     for tile in (True, False):
-        assert_same(r.denoise(color, sub, tile=tile, **kw), ref)
+        assert_same_bits(r.denoise(color, sub, tile=tile, **kw), ref)
     if not subset:   # a NULL guides struct through the C call
         out = np.empty_like(ref)
         p = abi.XrtDenoiseParams(color.shape[1], color.shape[0], kw["iterations"], kw["sigma_color"], kw["sigma_normal"],
                                  kw["sigma_depth"], kw["sigma_albedo"], 0)
         assert abi.lib().xrt_denoise(r.ctx, C.byref(p), color.ctypes.data, None, out.ctypes.data, None) == 0
-        assert_same(out, ref)
+        assert_same_bits(out, ref)
 
 
 # 3. a sigma <= 0 equals that plane being NULL
@@ -78,10 +59,10 @@ def test_sigma_off_equals_null_plane(r, plane, sigma):
     kw = dr.CASES["synthetic_2"][3]
     without = r.denoise(color, {k: v for k, v in g.items() if k != plane}, **kw)
     for off in (0.0, -1.0):
-        assert_same(r.denoise(color, g, **dict(kw, **{sigma: off})), without)
+        assert_same_bits(r.denoise(color, g, **dict(kw, **{sigma: off})), without)
     # sigma_color off: the restatement's frame
     off = dict(kw, sigma_color=0.0)
-    assert_same(r.denoise(color, g, **off), dr.denoise(color, g, **off))
+    assert_same_bits(r.denoise(color, g, **off), dr.denoise(color, g, **off))
 
 
 # 4. in place
@@ -91,7 +72,7 @@ def test_in_place(r, tile):
     kw = dr.CASES["130x70"][3]
     buf = np.array(color)
     assert r.denoise(buf, g, out=buf, tile=tile, **kw) is buf
-    assert_same(buf, dr.reference("130x70")[0])
+    assert_same_bits(buf, dr.reference("130x70")[0])
 
 
 # 5. the device entry point: torch tensors written on the current stream right before the call, guard
@@ -127,7 +108,7 @@ def test_device_entry_point(devices):
             torch.cuda.synchronize()
             got = out.cpu().numpy()
             assert (got[:pad] == -7.0).all() and (got[pad + n:] == -7.0).all()
-            assert_same(got[pad:pad + n].reshape(h, w, 3), ref)
+            assert_same_bits(got[pad:pad + n].reshape(h, w, 3), ref)
             if not in_place:
                 assert np.array_equal(src.cpu().numpy(), np.array(color).reshape(-1))   # the input is only read
     finally:
@@ -149,8 +130,8 @@ def test_null_color_is_the_last_render(devices):
         guides = hr.render_aov(s, w, h, planes=dr.GUIDES)
         kw = dict(iterations=2, sigma_depth=32.0)
         from_fb = hr.denoise(None, guides, width=w, height=h, **kw)
-        assert_same(from_fb, hr.denoise(frame, guides, **kw))
-        assert_same(from_fb, dr.denoise(frame, guides, **dict(dr.DEFAULTS, **kw)))
+        assert_same_bits(from_fb, hr.denoise(frame, guides, **kw))
+        assert_same_bits(from_fb, dr.denoise(frame, guides, **dict(dr.DEFAULTS, **kw)))
         # a frame larger than the framebuffer is refused
         p = abi.XrtDenoiseParams(4 * w, 4 * h, 1, 2.0, 0.0, 0.0, 0.0, 0)
         big = np.zeros((4 * h, 4 * w, 3), np.float32)
@@ -206,7 +187,7 @@ def test_render_guides_denoise():
         got = hr.denoise(frame, guides, **kw)
     finally:
         hr.close()
-    assert_same(got, dr.denoise(frame, guides, **kw))
+    assert_same_bits(got, dr.denoise(frame, guides, **kw))
     assert not np.array_equal(words(got), words(frame))
 
 
@@ -226,18 +207,11 @@ def example_scene(w, h):
 def test_denoise_example_ppm(tmp_path):
     w, h, spp = 48, 36, 4
     prefix = tmp_path / "frame"
-    subprocess.run([os.path.join(ROOT, "examples", "bin", "denoise"), str(w), str(h), str(spp), str(prefix)], check=True,
-                   capture_output=True, text=True)
-
-    def ppm(path):
-        tok = path.read_text().split()
-        assert tok[:4] == ["P3", str(w), str(h), "255"]
-        return np.array(tok[4:], np.int64).reshape(h, w, 3)
-
+    run_example("denoise", w, h, spp, prefix)
     s = example_scene(w, h)
     frame, _ = pyoracle.render(s, w, h, spp)
     planes, _, _ = ar.render(s, w, h, spp)
     assert frame.max() > 0
-    assert np.array_equal(ppm(tmp_path / "frame.noisy.ppm"), pyoracle.tonemap(frame, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "frame.noisy.ppm", w, h), pyoracle.tonemap(frame, 1.2).astype(np.int64))
     want = dr.denoise(frame, planes, **dr.DEFAULTS)
-    assert np.array_equal(ppm(tmp_path / "frame.denoised.ppm"), pyoracle.tonemap(want, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "frame.denoised.ppm", w, h), pyoracle.tonemap(want, 1.2).astype(np.int64))

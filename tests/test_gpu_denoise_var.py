@@ -4,8 +4,6 @@ the default path and under XRT_DENOISE_NO_TILE.  The cases and the situations th
 are in tests/denoise_var_restatement.py and checked without a GPU in
 tests/test_denoise_var_restatement.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,29 +12,12 @@ import aov_restatement as ar
 import denoise_restatement as dr
 import denoise_var_restatement as dv
 import pyoracle
+from gpu_checks import assert_same_bits, read_ppm, run_example, words
+from gpu_checks import renderer as r  # noqa: F401 -- the shared fixture, under the name the tests here ask for
 from xraytracer_amd import abi, scenes
 from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def words(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_same(got, ref):
-    assert got.shape == ref.shape and got.dtype == np.float32
-    d = np.argwhere(words(got) != words(ref))
-    assert len(d) == 0, (len(d), [(tuple(int(x) for x in q), got[tuple(q)].item(), ref[tuple(q)].item()) for q in d[:4]])
-
-
-@pytest.fixture(scope="module")
-def r():
-    h = HipRenderer(1)
-    yield h
-    h.close()
 
 
 def check_stats(st, iterations, tile, estimated):
@@ -54,8 +35,8 @@ def test_cases(r, name, tile):
     got, var = r.denoise_var(color, g, variance, tile=tile, **kw)
     check_stats(r.denoise_stats, kw["iterations"], tile, variance is None)
     ref, ref_var, _ = dv.reference(name)
-    assert_same(got, ref)
-    assert_same(var, ref_var)
+    assert_same_bits(got, ref)
+    assert_same_bits(var, ref_var)
 
 
 # 2. the estimate fed back as the caller's variance gives the bits of variance = NULL
@@ -67,8 +48,8 @@ def test_estimate_equals_supplied_estimate(r, name):
     for tile in (True, False):
         got, var = r.denoise_var(color, g, est, tile=tile, **kw)
         check_stats(r.denoise_stats, kw["iterations"], tile, False)
-        assert_same(got, dv.reference(name)[0])
-        assert_same(var, dv.reference(name)[1])
+        assert_same_bits(got, dv.reference(name)[0])
+        assert_same_bits(var, dv.reference(name)[1])
 
 
 # 3. guide-plane subsets: a plane left out is a plane of zeros
@@ -80,16 +61,16 @@ def test_plane_subsets(r, subset):
     ref, ref_var = dv.denoise_var(color, sub, None, **kw)
     for tile in (True, False):
         got, var = r.denoise_var(color, sub, tile=tile, **kw)
-        assert_same(got, ref)
-        assert_same(var, ref_var)
+        assert_same_bits(got, ref)
+        assert_same_bits(var, ref_var)
     if not subset:   # a NULL guides struct through the C call
         out, outv = np.empty_like(ref), np.empty_like(ref_var)
         p = abi.XrtDenoiseVarParams(color.shape[1], color.shape[0], kw["iterations"], kw["sigma_luminance"], kw["sigma_normal"],
                                     kw["sigma_depth"], kw["sigma_albedo"], kw["variance_radius"], 0)
         assert abi.lib().xrt_denoise_var(r.ctx, C.byref(p), color.ctypes.data, None, None, out.ctypes.data, outv.ctypes.data,
                                          None) == 0
-        assert_same(out, ref)
-        assert_same(outv, ref_var)
+        assert_same_bits(out, ref)
+        assert_same_bits(outv, ref_var)
 
 
 # 4. each sigma <= 0: the guide sigmas equal that plane being NULL, sigma_luminance the restatement's
@@ -101,8 +82,8 @@ def test_sigma_off_equals_null_plane(r, plane, sigma):
     without = r.denoise_var(color, {k: v for k, v in g.items() if k != plane}, **kw)
     for off in (0.0, -1.0):
         got = r.denoise_var(color, g, **dict(kw, **{sigma: off}))
-        assert_same(got[0], without[0])
-        assert_same(got[1], without[1])
+        assert_same_bits(got[0], without[0])
+        assert_same_bits(got[1], without[1])
 
 
 def test_sigma_luminance_off(r):
@@ -115,9 +96,9 @@ def test_sigma_luminance_off(r):
         ref, ref_var = dv.denoise_var(color, g, None, **o)
         for tile in (True, False):
             got, var = r.denoise_var(color, g, tile=tile, **o)
-            assert_same(got, ref)
-            assert_same(var, ref_var)
-            assert_same(got, plain)
+            assert_same_bits(got, ref)
+            assert_same_bits(var, ref_var)
+            assert_same_bits(got, plain)
 
 
 # 5. out_variance NULL
@@ -126,7 +107,7 @@ def test_no_variance_output(r):
     kw = dv.CASES["supplied"][4]
     got, var = r.denoise_var(color, g, variance, want_variance=False, **kw)
     assert var is None
-    assert_same(got, dv.reference("supplied")[0])
+    assert_same_bits(got, dv.reference("supplied")[0])
 
 
 # 6. in place, for both colour and variance
@@ -137,13 +118,13 @@ def test_in_place(r, tile):
     buf, vbuf = np.array(color), np.array(variance)
     got = r.denoise_var(buf, g, vbuf, out=buf, out_variance=vbuf, tile=tile, **kw)
     assert got[0] is buf and got[1] is vbuf
-    assert_same(buf, dv.reference("supplied")[0])
-    assert_same(vbuf, dv.reference("supplied")[1])
+    assert_same_bits(buf, dv.reference("supplied")[0])
+    assert_same_bits(vbuf, dv.reference("supplied")[1])
     color, g, _ = dv.inputs("130x70")
     buf = np.array(color)
     got = r.denoise_var(buf, g, out=buf, tile=tile, **dv.CASES["130x70"][4])
-    assert_same(buf, dv.reference("130x70")[0])
-    assert_same(got[1], dv.reference("130x70")[1])
+    assert_same_bits(buf, dv.reference("130x70")[0])
+    assert_same_bits(got[1], dv.reference("130x70")[1])
 
 
 # 7. the device entry point: torch tensors written on the current stream right before the call, guard
@@ -185,8 +166,8 @@ def test_device_entry_point(devices):
             got, gotv = out.cpu().numpy(), outv.cpu().numpy()
             assert (got[:pad] == -7.0).all() and (got[pad + n:] == -7.0).all()
             assert (gotv[:pad] == -7.0).all() and (gotv[pad + nv:] == -7.0).all()
-            assert_same(got[pad:pad + n].reshape(h, w, 3), ref)
-            assert_same(gotv[pad:pad + nv].reshape(h, w), ref_var)
+            assert_same_bits(got[pad:pad + n].reshape(h, w, 3), ref)
+            assert_same_bits(gotv[pad:pad + nv].reshape(h, w), ref_var)
             if not in_place:   # the inputs are only read
                 assert np.array_equal(src.cpu().numpy(), np.array(color).reshape(-1))
                 if variance is not None:
@@ -214,8 +195,8 @@ def test_null_color_is_the_last_render(devices):
         direct = hr.denoise_var(frame, guides, **kw)
         ref = dv.denoise_var(frame, guides, None, **dict(dv.DEFAULTS, **kw))
         for k in (0, 1):
-            assert_same(from_fb[k], direct[k])
-            assert_same(from_fb[k], ref[k])
+            assert_same_bits(from_fb[k], direct[k])
+            assert_same_bits(from_fb[k], ref[k])
         # a frame larger than the framebuffer is refused
         p = abi.XrtDenoiseVarParams(4 * w, 4 * h, 1, 4.0, 0.0, 0.0, 0.0, 2, 0)
         big = np.zeros((4 * h, 4 * w, 3), np.float32)
@@ -279,11 +260,11 @@ def test_filters_alternate_in_one_context():
             for name in ("130x70", "supplied"):
                 color, g, variance = dv.inputs(name)
                 got, var = hr.denoise_var(color, g, variance, tile=tile, **dv.CASES[name][4])
-                assert_same(got, dv.reference(name)[0])
-                assert_same(var, dv.reference(name)[1])
+                assert_same_bits(got, dv.reference(name)[0])
+                assert_same_bits(var, dv.reference(name)[1])
                 plain.append(hr.denoise(plain_color, plain_g, tile=tile, **plain_kw))
-                assert_same(plain[-1], dr.reference("synthetic_3")[0])
-            assert_same(plain[0], plain[1])
+                assert_same_bits(plain[-1], dr.reference("synthetic_3")[0])
+            assert_same_bits(plain[0], plain[1])
     finally:
         hr.close()
 
@@ -302,8 +283,8 @@ def test_render_guides_denoise_var():
     finally:
         hr.close()
     ref, ref_var = dv.denoise_var(frame, guides, None, **kw)
-    assert_same(got, ref)
-    assert_same(var, ref_var)
+    assert_same_bits(got, ref)
+    assert_same_bits(var, ref_var)
     assert not np.array_equal(words(got), words(frame))
 
 
@@ -311,14 +292,7 @@ def test_render_guides_denoise_var():
 def test_denoise_var_example_ppm(tmp_path):
     w, h, spp = 48, 36, 4
     prefix = tmp_path / "frame"
-    subprocess.run([os.path.join(ROOT, "examples", "bin", "denoise_var"), str(w), str(h), str(spp), str(prefix)], check=True,
-                   capture_output=True, text=True)
-
-    def ppm(path):
-        tok = path.read_text().split()
-        assert tok[:4] == ["P3", str(w), str(h), "255"]
-        return np.array(tok[4:], np.int64).reshape(h, w, 3)
-
+    run_example("denoise_var", w, h, spp, prefix)
     # examples/denoise.cpp's scene: the example's plane and sphere under a QuadLight, GIIntegrator(3)
     s = scenes.SceneBundle()
     s.add_mesh("plane", scenes.EXAMPLE_PLANE, (1.0, 1.0, 1.0))
@@ -330,6 +304,6 @@ def test_denoise_var_example_ppm(tmp_path):
     frame, _ = pyoracle.render(s, w, h, spp)
     planes, _, _ = ar.render(s, w, h, spp)
     assert frame.max() > 0
-    assert np.array_equal(ppm(tmp_path / "frame.noisy.ppm"), pyoracle.tonemap(frame, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "frame.noisy.ppm", w, h), pyoracle.tonemap(frame, 1.2).astype(np.int64))
     want, _ = dv.denoise_var(frame, planes, None, **dv.DEFAULTS)
-    assert np.array_equal(ppm(tmp_path / "frame.denoised.ppm"), pyoracle.tonemap(want, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(tmp_path / "frame.denoised.ppm", w, h), pyoracle.tonemap(want, 1.2).astype(np.int64))

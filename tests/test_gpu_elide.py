@@ -15,39 +15,20 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, assert_same_bits, counters_equal, render_pair, renderer  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 import elide_scenes as es
 
 pytestmark = pytest.mark.gpu
 
 
-def compare(img, ref):
-    assert img.shape == ref.shape and not np.any(np.isnan(ref))
-    bad = np.argwhere(np.any(img.view(np.uint32) != ref.view(np.uint32), axis=-1))
-    assert len(bad) == 0, (len(bad), bad[:5], img[tuple(bad[0])], ref[tuple(bad[0])])
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(1, device=0)
-    yield r
-    r.close()
-
-
 def render_elide(r, scene, w, h, spp, ref=None, **kw):
     """the device's frame and the oracle's (`ref`: an (image, stats) pair computed before), the
     counters compared; a camera-list launch beside k_seed shows that the pixels were tested"""
-    r.spp = spp
-    r._uploaded = None
-    img = r.render(scene, w, h, timing=True, **kw)
-    g = r.stats
-    okw = {k: v for k, v in kw.items() if k in ("shard_index", "shard_count", "initial")}
-    ref, st = ref if ref is not None else pyoracle.render(scene, w, h, spp, **okw)
+    img, ref, st, g = render_pair(r, scene, w, h, spp, ref=ref, timing=True, **kw)
     assert g.schedule == abi.XRT_SCHED_STEP_MERGED and g.launches[abi.XRT_K_SEED] == 2
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected) == \
-        (st["segments"], st["shadow_rays"], st["draws"], st["rejected"])
+    counters_equal(g, st, ("segments", "shadow_rays", "draws", "rejected"))
     return img, ref, st, g
 
 
@@ -68,7 +49,7 @@ def test_all_empty_frame(renderer):
     init[rng.random((h, w, 3)) < 0.1] = -0.0
     assert np.signbit(init).sum() > 100
     img, ref, st, g = render_elide(renderer, s, w, h, spp, initial=init)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert not np.any(np.signbit(img))
     assert g.rng_twists == g.path_slots == w * h
     assert g.launches[abi.XRT_K_STEP] < -(-spp // g.visits_per_launch)
@@ -87,7 +68,7 @@ def test_cornell_layouts(renderer, cornell_ref, spw, spec):
     slots that run for a hundred launches more, in every kernel that can be the first."""
     s, ref = cornell_ref
     img, ref, st, g = render_elide(renderer, s, 64, 48, 40, ref=ref, slots_per_wave=spw, visits_per_launch=3, spec=spec)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert g.visits_per_launch == 3 and g.slots_per_wave == spw
     if spw == 64:
         assert g.spec_launches == 0
@@ -117,7 +98,7 @@ def test_silhouettes(renderer, name):
     s = es.SILHOUETTES[name]()
     check_silhouette(name, hits(s, w, h, spp))
     img, ref, st, g = render_elide(renderer, s, w, h, spp)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_cornell_far_from_origin(renderer):
@@ -129,7 +110,7 @@ def test_cornell_far_from_origin(renderer):
     edge = hit & ~(np.roll(hit, 1, 0) & np.roll(hit, -1, 0) & np.roll(hit, 1, 1) & np.roll(hit, -1, 1))
     assert hit.mean() > 0.5 and (~hit).mean() > 0.3 and edge.sum() > 100   # a silhouette all round the box
     img, ref, st, g = render_elide(renderer, s, w, h, spp)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_row_shard_accumulates(renderer):
@@ -143,6 +124,6 @@ def test_row_shard_accumulates(renderer):
     img, ref, st, g = render_elide(renderer, s, w, h, spp, initial=init, shard_index=3, shard_count=8)
     owned = np.zeros(h, bool)
     owned[3::8] = True
-    compare(img[owned], ref[owned])
-    assert np.array_equal(img[~owned].view(np.uint32), init[~owned].view(np.uint32))
+    assert_frame(img[owned], ref[owned])
+    assert_same_bits(img[~owned], init[~owned])
     assert g.path_slots == owned.sum() * w

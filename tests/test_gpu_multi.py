@@ -151,11 +151,10 @@ def test_multi_setter_errors_name_the_device(single):
 
 def test_cpp_multi_gpu_renderer(tmp_path):
     """examples/cornellbox.cpp with a device list: HipRenderer(spp, cam, integ, {0, 0})."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "examples", "bin", "cornellbox")
+    from gpu_checks import DATA_DIR, run_example
+
     out = tmp_path / "fb.raw"
-    env = dict(os.environ, XRT_DATA_DIR=os.path.join(root, "xraytracer_amd", "data") + "/")
-    subprocess.check_call([exe, "64", "48", "4", "gi", str(out), "0,0"], env=env)
+    run_example("cornellbox", 64, 48, 4, "gi", out, "0,0", env={"XRT_DATA_DIR": DATA_DIR})
     img = np.fromfile(out, dtype=np.float32).reshape(48, 64, 3)
     ref, _ = pyoracle.render(scenes.cornell(64, 48), 64, 48, 4)
     assert np.array_equal(img, ref)
@@ -280,9 +279,9 @@ def test_bench_runs_ranks_over_rccl(tmp_path):
     the framebuffer) and reports n_gpus 2; the reduce time is reported on its own."""
     import json
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from gpu_checks import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--spp", "8", "--no-cpu"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]

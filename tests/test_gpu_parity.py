@@ -1,7 +1,7 @@
 """GPU parity: libxrt_hip.so (through the C ABI) against the oracle and the reference's
-golden vectors.  Bar: bit-exact pixels (the device path restates every float op of the
-reference, incl. glibc sinf/cosf); RMSE < 1e-3 per channel is the north-star tolerance and
-is asserted as a backstop on every image.
+golden vectors.  Bar: bit-exact pixels, the sign of a zero included (the device path restates
+every float op of the reference, incl. glibc sinf/cosf), which gpu_checks.assert_frame asserts
+on every image; the north-star tolerance, RMSE < 1e-3 per channel, follows from it.
 """
 import ctypes as C
 
@@ -9,29 +9,10 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import DATA_DIR, assert_frame, counters_equal, render_pair, renderer, run_example  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
-
-RMSE_TOL = 1e-3  # BASELINE.json north_star: per-channel RMSE < 1e-3 at matched seeds
-
-
-def compare(img, ref, min_exact=1.0):
-    assert img.shape == ref.shape
-    assert np.all(np.isfinite(img))
-    exact = float(np.mean(np.all(img == ref, axis=-1)))
-    rmse = np.sqrt(np.mean((img.astype(np.float64) - ref.astype(np.float64)) ** 2, axis=(0, 1)))
-    assert np.all(rmse < RMSE_TOL), rmse
-    assert exact >= min_exact, (exact, rmse, np.argwhere(~np.all(img == ref, axis=-1))[:5])
-    return exact, rmse
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(16, device=0)
-    yield r
-    r.close()
 
 
 @pytest.fixture(params=["auto", "step_tri", "wavefront"])
@@ -49,17 +30,13 @@ EXPECT_TRI = {"auto": abi.XRT_SCHED_STEP_MERGED, "step_tri": abi.XRT_SCHED_STEP_
               "wavefront": abi.XRT_SCHED_WAVEFRONT}
 
 
-GPU_ONLY = ("slots_per_wave", "visits_per_launch", "group", "deep", "timing")   # launch geometry, not semantics
+TRACED = ("segments", "shadow_rays", "draws")
 
 
 def render_both(r, scene, w, h, spp, schedule="auto", **kw):
-    r.spp = spp
-    r._uploaded = None
-    img = r.render(scene, w, h, schedule=schedule, **kw)
-    ref, st = pyoracle.render(scene, w, h, spp, **{k: v for k, v in kw.items() if k not in GPU_ONLY})
-    steps = r.stats.launches[abi.XRT_K_STEP]
+    img, ref, st, g = render_pair(r, scene, w, h, spp, schedule=schedule, **kw)
     if schedule == "wavefront":
-        assert steps == 0
+        assert g.launches[abi.XRT_K_STEP] == 0
     return img, ref, st
 
 
@@ -194,7 +171,7 @@ def test_tonemap_matches_reference_output_stage(renderer):
 
     s = scenes.cornell(64, 48)
     img, ref, _ = render_both(renderer, s, 64, 48, 4)
-    compare(img, ref)
+    assert_frame(img, ref)
     for gamma in (1.2, 2.2):
         assert np.array_equal(renderer.tonemap(64, 48, gamma), pyoracle.tonemap(ref, gamma))
     edge = np.array([0.0, 1e-40, 1e-3, 0.5, 1.0, 1.0001, 7.5, 3e9, 1e30, np.inf, np.nan, 1e-7], np.float32)
@@ -209,26 +186,25 @@ def test_c1_cornell_gi_bit_exact(renderer, sched):
     """Config C1 (Cornell 256x256x16, GIIntegrator(3)) — full framebuffer vs oracle."""
     s = scenes.cornell(256, 256)
     img, ref, st = render_both(renderer, s, 256, 256, 16, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert (g.launches[abi.XRT_K_STEP] > 0) == (sched != "wavefront")
     assert g.schedule == EXPECT_TRI[sched]
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected) == (st["segments"], st["shadow_rays"], st["draws"],
-                                                                st["rejected"])
+    counters_equal(g, st, TRACED + ("rejected",))
 
 
 def test_cornell_gi_nonsquare_and_depths(renderer, sched):
     s = scenes.cornell(80, 60)
     for depth in (1, 2, 5):
         img, ref, st = render_both(renderer, s, 80, 60, 8, max_depth=depth, schedule=sched)
-        compare(img, ref)
+        assert_frame(img, ref)
         assert renderer.stats.draws == st["draws"]
 
 
 def test_cornell_direct(renderer, sched):
     s = scenes.cornell(96, 72)
     img, ref, _ = render_both(renderer, s, 96, 72, 8, integrator="direct", schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_deep_streams_wrap_the_ring(renderer, sched):
@@ -238,7 +214,7 @@ def test_deep_streams_wrap_the_ring(renderer, sched):
     s = scenes.cornell(16, 12)
     for spp, kw in ((400, {}), (640, {"integrator": "direct"})):
         img, ref, st = render_both(renderer, s, 16, 12, spp, schedule=sched, **kw)
-        compare(img, ref)
+        assert_frame(img, ref)
         assert renderer.stats.draws == st["draws"]
         assert st["draws"] / (16 * 12) > 2 * 1248 - 624   # the stream starts at word 624
 
@@ -248,13 +224,13 @@ def test_edge_sizes(renderer, wh, sched):
     w, h = wh
     s = scenes.cornell(w, h)
     img, ref, _ = render_both(renderer, s, w, h, 3, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_spp_one_and_depth_zero(renderer, sched):
     s = scenes.cornell(40, 30)
     img, ref, _ = render_both(renderer, s, 40, 30, 1, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     img, ref, _ = render_both(renderer, s, 40, 30, 4, max_depth=0, schedule=sched)
     assert np.all(img == 0) and np.all(ref == 0)
 
@@ -267,10 +243,10 @@ def test_merged_segments_per_launch(renderer, visits):
     s = scenes.cornell(24, 18)
     for kw in ({}, {"integrator": "direct"}, {"max_depth": 5}):
         img, ref, st = render_both(renderer, s, 24, 18, 6, visits_per_launch=visits, schedule="step", **kw)
-        compare(img, ref)
+        assert_frame(img, ref)
         g = renderer.stats
         assert g.schedule == abi.XRT_SCHED_STEP_MERGED and g.visits_per_launch == visits
-        assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+        counters_equal(g, st, TRACED)
 
 
 @pytest.mark.parametrize("spw,group", [(4, True), (16, True), (32, True), (64, True), (16, False), (32, False)])
@@ -281,18 +257,18 @@ def test_merged_slots_per_wave(renderer, spw, group):
     s = scenes.cornell(40, 30)
     for kw in ({}, {"integrator": "direct"}):
         img, ref, st = render_both(renderer, s, 40, 30, 5, slots_per_wave=spw, group=group, schedule="step", **kw)
-        compare(img, ref)
+        assert_frame(img, ref)
         g = renderer.stats
         assert g.schedule == abi.XRT_SCHED_STEP_MERGED
         assert (g.slots_per_wave, g.group_lanes) == (spw, 64 // spw if group and spw < 64 else 1)
-        assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+        counters_equal(g, st, TRACED)
 
 
 def test_shards_reassemble_exactly(renderer):
     """Row-interleaved pixel shards (the multi-GPU split) sum to the 1-shard image bit-exactly."""
     s = scenes.cornell(48, 37)
     renderer.spp = 4
-    renderer._uploaded = None
+    renderer.upload(s)
     full = renderer.render(s, 48, 37)
     acc = np.zeros_like(full)
     for k in range(3):
@@ -307,7 +283,7 @@ def test_c3_spheres_direct(renderer, sched):
     """Config C3 scene (1000 spheres + sphere light, DirectIntegrator) at reduced size."""
     s = scenes.spheres(160, 90)
     img, ref, st = render_both(renderer, s, 160, 90, 4, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.schedule == {"wavefront": abi.XRT_SCHED_WAVEFRONT, "step_tri": abi.XRT_SCHED_STEP,
                                        "auto": abi.XRT_SCHED_PIXEL}[sched]
     assert renderer.stats.shadow_rays == st["shadow_rays"]
@@ -335,7 +311,7 @@ def test_sphere_bvh_ties_and_gi(renderer, sched, integ):
     broken by iteration order), GI bounces between spheres, Direct."""
     s = dup_spheres(64, 48)
     img, ref, st = render_both(renderer, s, 64, 48, 4, integrator=integ, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.segments == st["segments"]
     assert renderer.stats.shadow_rays == st["shadow_rays"]
 
@@ -346,7 +322,7 @@ def test_indirect_and_normal_integrators(renderer, sched, integ, depth):
     Cornell box (triangles) and the sphere scene, bit-exact against the oracle."""
     for s, w, h in ((scenes.cornell(64, 48), 64, 48), (dup_spheres(48, 36), 48, 36)):
         img, ref, st = render_both(renderer, s, w, h, 4, integrator=integ, max_depth=depth, schedule=sched)
-        compare(img, ref)
+        assert_frame(img, ref)
         assert renderer.stats.segments == st["segments"]
         assert renderer.stats.draws == st["draws"]
 
@@ -356,7 +332,7 @@ def test_normal_integrator_on_medium_box(renderer, sched):
     default (0), so the pixel is 0.5 — as in the reference."""
     s = scenes.smoke(32, 24)
     img, ref, _ = render_both(renderer, s, 32, 24, 2, integrator="normal", schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 @pytest.mark.parametrize("integ,schedule", [("indirect", "auto"), ("normal", "step"), ("gi", "step_tri")])
@@ -377,10 +353,10 @@ def test_kstep_refill_staging_beside_a_large_scene(renderer, integ, schedule):
     spp = 160 if integ == "normal" else 64   # Normal draws 2 words per sample: 160 spp to run low
     img, ref, st = render_both(renderer, s, 40, 30, spp, integrator=integ, max_depth=3, schedule=schedule,
                                timing=True)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert g.schedule == abi.XRT_SCHED_STEP   # the layout leaves no room for k_step_tri's scratch
-    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+    counters_equal(g, st, TRACED)
     assert g.launches[abi.XRT_K_REFILL] == 1 and g.rng_twists - g.path_slots > g.path_slots // 4
 
 
@@ -397,14 +373,14 @@ def test_c4_sphere_mesh_gi(renderer, nt, w, h, spp, deep):
         img, ref, st = render_both(renderer, s, w, h, spp, schedule="auto")
     else:
         img, ref, st = render_both(renderer, s, w, h, spp, deep=deep, schedule="wavefront")
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     if deep == "fused":
         assert g.schedule == abi.XRT_SCHED_STEP_BVH and g.launches[abi.XRT_K_DEEP] == 0
     else:
         assert g.launches[abi.XRT_K_STEP] == 0   # multi-pass schedule
         assert g.schedule == abi.XRT_SCHED_WAVEFRONT
-    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+    counters_equal(g, st, TRACED)
 
 
 @pytest.mark.parametrize("integ", ["gi", "direct"])
@@ -424,12 +400,12 @@ def test_two_level_fused_layouts_and_lights(renderer, integ, spw):
     s.camera = scenes.pinhole(scenes.CORNELL_C2W, 60.0, 72, 40)
     img, ref, st = render_both(renderer, s, 72, 40, 5, integrator=integ, schedule="auto", slots_per_wave=spw,
                                visits_per_launch=3)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert g.schedule == abi.XRT_SCHED_STEP_BVH and g.launches[abi.XRT_K_STEP] > 2
     if spw:
         assert g.layout_launches[abi.LAYOUTS.index(spw)] == g.launches[abi.XRT_K_STEP]
-    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+    counters_equal(g, st, TRACED)
 
 
 def two_light_two_level(w, h, extra=0):
@@ -453,10 +429,10 @@ def two_light_two_level(w, h, extra=0):
 
 def check_two_level_wavefront(renderer, s, integ, deep):
     img, ref, st = render_both(renderer, s, 48, 30, 3, integrator=integ, deep=deep, schedule="wavefront")
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert g.schedule == abi.XRT_SCHED_WAVEFRONT and g.launches[abi.XRT_K_DEEP] > 0 and g.shadow_rays > 0
-    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+    counters_equal(g, st, TRACED)
 
 
 @pytest.mark.parametrize("integ", ["gi", "direct"])
@@ -484,9 +460,9 @@ def test_triangle_light_and_two_lights(renderer, sched):
     s.flatten()
     s.camera = scenes.pinhole(scenes.CORNELL_C2W, 60.0, 64, 48)
     img, ref, _ = render_both(renderer, s, 64, 48, 4, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     img, ref, _ = render_both(renderer, s, 64, 48, 4, integrator="direct", schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_c5_smoke_vpt(renderer, sched):
@@ -494,7 +470,7 @@ def test_c5_smoke_vpt(renderer, sched):
     VolumePathTracing(10)) at reduced grid and image size."""
     s = scenes.smoke(48, 36, n=32)
     img, ref, st = render_both(renderer, s, 48, 36, 4, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert g.draws == st["draws"] and g.segments == st["segments"] and g.stalled == st["stalled"] == 0
 
@@ -511,7 +487,7 @@ def test_grid_signed_zeros_and_denormals(renderer, sched):
     g[20:28, 0:8, 0:8] = 0.0
     g[23, 5, 6] = np.float32(1e-40)
     img, ref, st = render_both(renderer, s, 40, 30, 4, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.draws == st["draws"]
 
 
@@ -519,7 +495,7 @@ def test_vpt_medium_walk_suspends_and_resumes(renderer, sched):
     """Many spp per pixel forces delta-tracking walks to cross RNG refills (suspend/resume)."""
     s = scenes.smoke(12, 9, n=32)
     img, ref, st = render_both(renderer, s, 12, 9, 96, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.draws == st["draws"]
 
 
@@ -531,10 +507,10 @@ def test_vpt_events_resume_across_launches(renderer, visits, integ):
     launch end and resumed by the next launch.  Bit-exact, same draws and segments."""
     s = dense_smoke(20, 15) if integ == "vpt_nee" else scenes.smoke(20, 15, n=32)
     img, ref, st = render_both(renderer, s, 20, 15, 6, integrator=integ, visits_per_launch=visits)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
     assert g.visits_per_launch == visits
-    assert g.draws == st["draws"] and g.segments == st["segments"]
+    counters_equal(g, st, ("draws", "segments"))
 
 
 def dense_smoke(w, h, n=24, g=0.4):
@@ -574,9 +550,9 @@ def test_homogeneous_media(renderer, sched, kind, integ):
     transmittance on the NEE shadow ray), bit-exact against the oracle."""
     s = homog_scene(kind, 40, 30)
     img, ref, st = render_both(renderer, s, 40, 30, 4, integrator=integ, schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
-    assert g.draws == st["draws"] and g.segments == st["segments"] and g.shadow_rays == st["shadow_rays"]
+    counters_equal(g, st, TRACED)
 
 
 @pytest.mark.parametrize("dense", [False, True])
@@ -585,9 +561,9 @@ def test_vpt_nee(renderer, sched, dense):
     event, shadow ray's closest hit, ratio-tracking transmittance through the medium."""
     s = dense_smoke(40, 30) if dense else scenes.smoke(40, 30, n=32)
     img, ref, st = render_both(renderer, s, 40, 30, 4, integrator="vpt_nee", schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     g = renderer.stats
-    assert g.draws == st["draws"] and g.segments == st["segments"] and g.shadow_rays == st["shadow_rays"]
+    counters_equal(g, st, TRACED)
     assert st["shadow_rays"] > 0
 
 
@@ -596,7 +572,7 @@ def test_vpt_nee_ratio_tracking_suspends_and_resumes(renderer, sched):
     runs out of RNG words mid-walk and resumes after the refill."""
     s = dense_smoke(8, 6)
     img, ref, st = render_both(renderer, s, 8, 6, 160, integrator="vpt_nee", schedule=sched)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert renderer.stats.draws == st["draws"]
 
 
@@ -604,14 +580,9 @@ def test_vpt_nee_ratio_tracking_suspends_and_resumes(renderer, sched):
 def test_cpp_api_example_matches_oracle(tmp_path, kind):
     """examples/cornellbox.cpp — the reference example written against include/xrt/*.h with
     HipRenderer — renders the same image as the oracle, bit for bit."""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "examples", "bin", "cornellbox")
     out = tmp_path / "fb.raw"
-    env = dict(os.environ, XRT_DATA_DIR=os.path.join(root, "xraytracer_amd", "data") + "/")
-    subprocess.check_call([exe, "64", "48", "4", kind, str(out)], env=env)
+    run_example("cornellbox", 64, 48, 4, kind, out, env={"XRT_DATA_DIR": DATA_DIR})
     img = np.fromfile(out, dtype=np.float32).reshape(48, 64, 3)
     s = scenes.cornell(64, 48)
     ref, _ = pyoracle.render(s, 64, 48, 4, integrator=kind)
-    compare(img, ref)
+    assert_frame(img, ref)

@@ -15,41 +15,14 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, counters_equal, render_pair, renderer  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-RMSE_TOL = 1e-3  # BASELINE.json north_star: per-channel RMSE < 1e-3 at matched seeds
 
-
-def compare(img, ref):
-    assert img.shape == ref.shape
-    rmse = np.sqrt(np.mean((img.astype(np.float64) - ref.astype(np.float64)) ** 2, axis=(0, 1)))
-    assert np.all(rmse < RMSE_TOL), rmse
-    bad = np.argwhere(~np.all(img == ref, axis=-1))
-    assert len(bad) == 0, (len(bad), bad[:5], rmse)
-
-
-def counters_equal(g, st):
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected, g.stalled) == \
-        (st["segments"], st["shadow_rays"], st["draws"], st["rejected"], st["stalled"])
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(1, device=0)
-    yield r
-    r.close()
-
-
-def render_pixel(r, scene, w, h, spp, integrator=None, **kw):
-    r.spp = spp
-    r._uploaded = None
-    img = r.render(scene, w, h, integrator=integrator, timing=True, **kw)
-    g = r.stats
-    okw = {k: v for k, v in kw.items() if k in ("shard_index", "shard_count", "initial")}
-    ref, st = pyoracle.render(scene, w, h, spp, integrator=integrator, **okw)
+def render_pixel(r, scene, w, h, spp, **kw):
+    img, ref, st, g = render_pair(r, scene, w, h, spp, timing=True, **kw)
     assert g.schedule == abi.XRT_SCHED_PIXEL, g.schedule
     assert g.launches[abi.XRT_K_STEP] == 1 and g.launches[abi.XRT_K_REFILL] == 0, list(g.launches)
     return img, ref, st, g
@@ -87,7 +60,7 @@ def test_c3_family_long_chains(renderer):
     many times and walks ~8-16 windows per pixel."""
     s = scenes.spheres(48, 27)
     img, ref, st, g = render_pixel(renderer, s, 48, 27, 512)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert g.segments == 48 * 27 * 512
     assert st["draws"] > 48 * 27 * 512 * 2   # some samples hit surfaces and draw light words
@@ -102,7 +75,7 @@ def test_frustum_lists_and_their_overflow(renderer, wh):
     w, h = wh
     s = scenes.spheres(w, h)
     img, ref, st, g = render_pixel(renderer, s, w, h, 150)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     # which of k_pixel's paths ran (xrt_stats pix_*): every pixel builds a list or overflows
     assert g.pix_frustum + g.pix_frustum_overflow == w * h
@@ -138,7 +111,7 @@ def test_block_culled_lists_far_from_origin(renderer, wh):
     w, h = wh
     s = far_cluster(w, h)
     img, ref, st, g = render_pixel(renderer, s, w, h, 48)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert st["shadow_rays"] > 0
     assert g.pix_frustum > 0 and g.pix_shadow_list > 0 and g.pix_flushes > 0
@@ -151,7 +124,7 @@ def test_window_edges_two_lights(renderer, spp):
     a window and windows whose last sample's light words run past the window."""
     s = two_light_cornell(24, 18)
     img, ref, st, g = render_pixel(renderer, s, 24, 18, spp, integrator="direct")
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -159,7 +132,7 @@ def test_window_edges_two_lights(renderer, spp):
 def test_cornell_direct_one_light(renderer, spp):
     s = scenes.cornell(40, 30)
     img, ref, st, g = render_pixel(renderer, s, 40, 30, spp, integrator="direct")
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -167,7 +140,7 @@ def test_cornell_direct_one_light(renderer, spp):
 def test_sphere_bvh_ties(renderer, integ):
     s = dup_spheres(48, 36)
     img, ref, st, g = render_pixel(renderer, s, 48, 36, 96, integrator=integ)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
 
 
@@ -177,7 +150,7 @@ def test_normal_integrator_scenes(renderer, spp):
     mixed (medium box) scenes."""
     for s, w, h in ((scenes.cornell(32, 24), 32, 24), (dup_spheres(24, 18), 24, 18), (scenes.smoke(16, 12), 16, 12)):
         img, ref, st, g = render_pixel(renderer, s, w, h, spp, integrator="normal")
-        compare(img, ref)
+        assert_frame(img, ref)
         counters_equal(g, st)
 
 
@@ -193,7 +166,7 @@ def test_accumulate_and_rejects(renderer):
     s.camera = scenes.pinhole(scenes.CORNELL_C2W, 60.0, 32, 24)
     init = np.random.default_rng(3).uniform(0.0, 2.0, (24, 32, 3)).astype(np.float32)
     img, ref, st, g = render_pixel(renderer, s, 32, 24, 70, integrator="direct", initial=init)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert st["rejected"] > 1000
 
@@ -214,7 +187,7 @@ def test_deferred_shading_rejects_and_accumulate(renderer):
     init = np.random.default_rng(4).uniform(0.0, 2.0, (24, 32, 3)).astype(np.float32)
     for spp in (5, 64, 130, 191, 257):
         img, ref, st, g = render_pixel(renderer, s, 32, 24, spp, integrator="direct", initial=init)
-        compare(img, ref)
+        assert_frame(img, ref)
         counters_equal(g, st)
         assert st["rejected"] > 0
 
@@ -241,7 +214,7 @@ def test_shadow_occluder_lists(renderer, light):
     for w, h in ((48, 27), (13, 7)):
         s.camera = scenes.pinhole((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 2.5, 3, 1), 60.0, w, h)
         img, ref, st, g = render_pixel(renderer, s, w, h, 70, integrator="direct")
-        compare(img, ref)
+        assert_frame(img, ref)
         counters_equal(g, st)
         # the lists are built for pure sphere scenes (SCN_SPHERE): a quad or triangle light
         # adds a mesh object, and those scenes trace their shadow rays through the scene walk
@@ -276,7 +249,7 @@ def test_stride4_windows_on_a_covered_block(renderer):
     w, h = 16, 12
     s = covered_block(w, h)
     img, ref, st, g = render_pixel(renderer, s, w, h, 512)
-    compare(img, ref)
+    assert_frame(img, ref)
     counters_equal(g, st)
     assert st["draws"] == w * h * 512 * 4   # every sample: 2 jitter + 2 light words
     assert g.pix_stride4 == 7 * w * h and g.pix_windows == 9 * w * h
@@ -289,7 +262,7 @@ def test_shards_and_step_schedule_agree(renderer):
     per-slot fused schedule (XRT_FLAG_NO_PIXEL) renders the same image."""
     s = scenes.spheres(40, 22)
     renderer.spp = 40
-    renderer._uploaded = None
+    renderer.upload(s)
     full = renderer.render(s, 40, 22)
     assert renderer.stats.schedule == abi.XRT_SCHED_PIXEL
     acc = np.zeros_like(full)
@@ -328,7 +301,7 @@ def test_c3_headline_geometry(renderer):
     assert g.samples == 1280 * 720 * 96 and g.segments == 1280 * 720 * 96
     k, n = 21, 64
     ref, st = pyoracle.render(scene, 1280, 720, 96, shard_index=k, shard_count=n)
-    compare(img[k::n], ref[k::n])
+    assert_frame(img[k::n], ref[k::n])
 
 
 def test_c3_fast_paths_in_compared_rows(renderer):
@@ -343,8 +316,8 @@ def test_c3_fast_paths_in_compared_rows(renderer):
     assert g.pix_frustum > 0 and g.pix_shadow_list > 0 and g.pix_flushes > 0 and g.pix_stride4 > 0
     assert g.pix_frustum + g.pix_frustum_overflow == npx
     ref, st = pyoracle.render(scene, 1280, 720, 96, shard_index=29, shard_count=64)
-    compare(img[29::64], ref[29::64])
-    assert (g.shadow_rays, g.draws) == (st["shadow_rays"], st["draws"])
+    assert_frame(img[29::64], ref[29::64])
+    counters_equal(g, st, ("shadow_rays", "draws"))
 
 
 def test_c3_row_shard(renderer):
@@ -357,4 +330,4 @@ def test_c3_row_shard(renderer):
     owned[3::8] = True
     assert np.all(img[~owned] == 0)
     ref, _ = pyoracle.render(scene, 1280, 720, 24, shard_index=3, shard_count=64)
-    compare(img[3::64], ref[3::64])
+    assert_frame(img[3::64], ref[3::64])

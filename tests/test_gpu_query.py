@@ -4,13 +4,11 @@ answer caller rays — against the oracle's restatement of the reference, field 
 bit for bit; and the reference's host API (Sampler, PinholeCamera::sampleRay,
 Scene::sampleAreaLight, single-ray and batched Scene queries) through examples/scene_query.cpp.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import DATA_DIR, run_example
 from xraytracer_amd import scenes
 from xraytracer_amd.renderer import HipRenderer
 
@@ -18,7 +16,6 @@ from test_gpu_parity import two_light_two_level
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("hit", "object", "primitive", "t", "t1", "position", "ng", "ns", "dpdu", "dpdv", "barycentric")
 
 
@@ -102,8 +99,7 @@ def test_cpp_host_query_api(tmp_path):
     raw = tmp_path / "rays.raw"
     np.concatenate([rays, tmax[:, None]], axis=1).astype(np.float32).tofile(raw)
     out = tmp_path / "out.raw"
-    subprocess.check_call([os.path.join(ROOT, "examples", "bin", "scene_query"),
-                           os.path.join(ROOT, "xraytracer_amd", "data") + "/", str(raw), str(n), str(out)])
+    run_example("scene_query", DATA_DIR, raw, n, out)
     got = np.fromfile(out, np.float32)
     s = scenes.cornell(800, 600)
     ref = pyoracle.query(s, rays)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame
 from xraytracer_amd import scenes
 from xraytracer_amd.renderer import HipRenderer
 
@@ -41,7 +42,7 @@ def test_sparse_grid_renders_like_dense(schedule, integ):
     r = HipRenderer(spp, device=0)
     img = r.render(s, w, h, integrator=integ, schedule=schedule)
     ref, st = pyoracle.render(s, w, h, spp, integrator=integ)
-    assert np.array_equal(img, ref), np.argwhere(~np.all(img == ref, axis=-1))[:5]
+    assert_frame(img, ref)
     assert r.stats.draws == st["draws"] and r.stats.segments == st["segments"]
     r.close()
 
@@ -63,6 +64,6 @@ def test_sparse_grid_with_odd_dims_and_multiplier():
     r = HipRenderer(4, device=0)
     img = r.render(s, 48, 36)
     ref, st = pyoracle.render(s, 48, 36, 4)
-    assert np.array_equal(img, ref)
+    assert_frame(img, ref)
     assert st["shadow_rays"] > 0
     r.close()

@@ -18,39 +18,16 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_checks import assert_frame, counters_equal, render_pair, renderer  # noqa: F401
 from xraytracer_amd import abi, scenes
-from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-RMSE_TOL = 1e-3  # BASELINE.json north_star: per-channel RMSE < 1e-3 at matched seeds
-
-
-def compare(img, ref):
-    assert img.shape == ref.shape
-    rmse = np.sqrt(np.mean((img.astype(np.float64) - ref.astype(np.float64)) ** 2, axis=(0, 1)))
-    assert np.all(rmse < RMSE_TOL), rmse
-    bad = np.argwhere(~np.all(img == ref, axis=-1))
-    assert len(bad) == 0, (len(bad), bad[:5], rmse)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    r = HipRenderer(1, device=0)
-    yield r
-    r.close()
-
 
 def render_spec(r, scene, w, h, spp, force=True, spw=16, **kw):
-    r.spp = spp
-    r._uploaded = None
-    img = r.render(scene, w, h, timing=True, slots_per_wave=spw if force else 0, **kw)
-    g = r.stats
-    okw = {k: v for k, v in kw.items() if k in ("integrator", "max_depth", "shard_index", "shard_count", "initial")}
-    ref, st = pyoracle.render(scene, w, h, spp, **okw)
+    img, ref, st, g = render_pair(r, scene, w, h, spp, timing=True, slots_per_wave=spw if force else 0, **kw)
     assert g.schedule == abi.XRT_SCHED_STEP_MERGED
-    assert (g.segments, g.shadow_rays, g.draws, g.rejected) == \
-        (st["segments"], st["shadow_rays"], st["draws"], st["rejected"])
+    counters_equal(g, st, ("segments", "shadow_rays", "draws", "rejected"))
     return img, ref, st, g
 
 
@@ -58,7 +35,7 @@ def render_spec(r, scene, w, h, spp, force=True, spw=16, **kw):
 def test_cornell_every_launch_speculative(renderer, spp):
     s = scenes.cornell(64, 48)
     img, ref, st, g = render_spec(renderer, s, 64, 48, spp)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert g.spec_launches == g.launches[abi.XRT_K_STEP] > 0
 
 
@@ -68,7 +45,7 @@ def test_wider_groups(renderer, spw):
     widen the group trace), across launch boundaries."""
     s = scenes.cornell(40, 30)
     img, ref, st, g = render_spec(renderer, s, 40, 30, 11, spw=spw, visits_per_launch=3)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert g.spec_launches == g.launches[abi.XRT_K_STEP] > 5
 
 
@@ -79,7 +56,7 @@ def test_samples_and_shadow_rays_cross_launches(renderer, visits):
     drained or saved at the launch end and resumed by the next launch."""
     s = scenes.cornell(40, 30)
     img, ref, st, g = render_spec(renderer, s, 40, 30, 9, visits_per_launch=visits)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert g.visits_per_launch == visits and g.spec_launches > 5
 
 
@@ -87,7 +64,7 @@ def test_samples_and_shadow_rays_cross_launches(renderer, visits):
 def test_depths(renderer, depth):
     s = scenes.cornell(48, 36)
     img, ref, st, g = render_spec(renderer, s, 48, 36, 12, max_depth=depth)
-    compare(img, ref)
+    assert_frame(img, ref)
 
 
 def test_mixed_layouts_frame(renderer):
@@ -96,7 +73,7 @@ def test_mixed_layouts_frame(renderer):
     20k, the speculative 4-slot ones — slots move between the kernels mid-sample."""
     s = scenes.cornell(400, 300)
     img, ref, st, g = render_spec(renderer, s, 400, 300, 24, force=False, visits_per_launch=4)
-    compare(img, ref)
+    assert_frame(img, ref)
     ll = g.layout_launches
     assert g.spec_launches == ll[2] + ll[4] and ll[2] > 0 and ll[4] > 0 and ll[0] + ll[1] > 0
 
@@ -113,7 +90,7 @@ def test_rejects_and_accumulate(renderer):
     s.integrator, s.max_depth = "gi", 3
     init = np.random.default_rng(5).uniform(0.0, 2.0, (30, 40, 3)).astype(np.float32)
     img, ref, st, g = render_spec(renderer, s, 40, 30, 20, initial=init)
-    compare(img, ref)
+    assert_frame(img, ref)
     assert st["rejected"] > 100
 
 
@@ -136,15 +113,15 @@ def test_c2_row_shard(renderer):
     owned[3::8] = True
     assert np.all(img[~owned] == 0)
     ref, st = pyoracle.render(scene, w, h, 64, shard_index=3, shard_count=8)
-    compare(img[owned], ref[owned])
-    assert (g.segments, g.shadow_rays, g.draws) == (st["segments"], st["shadow_rays"], st["draws"])
+    assert_frame(img[owned], ref[owned])
+    counters_equal(g, st, ("segments", "shadow_rays", "draws"))
 
 
 def test_no_spec_flag_same_image(renderer):
     """XRT_FLAG_NO_SPEC keeps the 16-slot launches on k_step_merged: the same image and counters."""
     s = scenes.cornell(48, 36)
     renderer.spp = 16
-    renderer._uploaded = None
+    renderer.upload(s)
     a = renderer.render(s, 48, 36, slots_per_wave=16)
     ga = renderer.stats
     b = renderer.render(s, 48, 36, slots_per_wave=16, spec=False)

@@ -2,51 +2,24 @@
 (tests/whitted_restatement.py): every frame bit for bit, every counter for equality.  The
 scenes and the conditions they are chosen for are in tests/whitted_scenes.py and checked
 without a GPU in tests/test_whitted_restatement.py."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import pyoracle
 import whitted_scenes as ws
+from gpu_checks import ROOT, assert_frame, check_whitted_case, read_ppm, render_rc, run_example, words
 from xraytracer_amd import abi, scenes
 from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32),
-                          np.ascontiguousarray(b, np.float32).view(np.uint32))
-
-
-def first_diff(a, b):
-    d = np.argwhere(np.ascontiguousarray(a, np.float32).view(np.uint32) != np.ascontiguousarray(b, np.float32).view(np.uint32))
-    return [(tuple(int(x) for x in q), float(a[tuple(q)]), float(b[tuple(q)])) for q in d[:4]]
-
 
 def check_case(name, devices=None):
     """render CASES[name] on the GPU and compare frame and counters with the restatement"""
-    _, w, h, spp, depth, kw = ws.CASES[name]
-    kw = dict(kw)
-    initial = ws.initial_image(w, h) if kw.pop("initial", False) else None
-    ref, cnt, per = ws.reference(name)
-    r = HipRenderer(spp, devices=devices)
-    try:
-        img = r.render(ws.scene(name), w, h, initial=initial, max_depth=depth, **kw)
-        st = r.stats
-        assert st.schedule == abi.XRT_SCHED_WHITTED
-        got = {k: int(getattr(st, k)) for k in ws.COUNTERS}
-        assert got == {k: int(cnt[k]) for k in ws.COUNTERS}
-        assert same_bits(img, ref), first_diff(img, ref)
-    finally:
-        r.close()
-    return img, cnt, per
+    return check_whitted_case(ws, name, abi.XRT_SCHED_WHITTED, devices=devices)
 
 
 # 1. Lambert + both light kinds: the example scene, a shard of it, accumulation over an image
@@ -80,20 +53,6 @@ def test_glass_tree(name):
     depth = ws.CASES[name][4]
     assert cnt["whit_refract"] > 0 and cnt["whit_tir"] > 0 and cnt["whit_depth_cut"] > 0
     assert (per["cut"] == 2 ** (depth + 1)).any()
-
-
-def render_rc(scene, w, h, spp, **kw):
-    """xrt_render's status and message for a render that may be refused"""
-    r = HipRenderer(spp)
-    try:
-        r.upload(scene)
-        p = r.params(scene, w, h, **kw)
-        img = np.zeros((h, w, 3), np.float32)
-        st = abi.XrtStats()
-        rc = abi.lib().xrt_render(r.ctx, C.byref(p), abi.fptr(img), C.byref(st))
-        return rc, abi.lib().xrt_last_error(r.ctx).decode()
-    finally:
-        r.close()
 
 
 def test_glass_depth_limit():
@@ -153,7 +112,8 @@ def test_clearing_delta_lights():
         assert abi.lib().xrt_set_delta_lights(r.ctx, None, 0) == 0
         img = r.render(lit, w, h, max_depth=depth)   # same bundle: no re-upload
         assert r.stats.shadow_rays == 0
-        assert same_bits(img, ref) and not same_bits(img, with_lights)
+        assert_frame(img, ref)
+        assert not np.array_equal(words(img), words(with_lights))
     finally:
         r.close()
 
@@ -197,10 +157,6 @@ def test_device_whitted_math(gpu):
 def test_whitted_example_ppm(tmp_path):
     w, h, spp = 48, 36, 3
     out = tmp_path / "whitted.ppm"
-    subprocess.run([os.path.join(ROOT, "examples", "bin", "whitted"), str(w), str(h), str(spp), str(out)], check=True,
-                   capture_output=True, text=True)
-    tok = out.read_text().split()
-    assert tok[:4] == ["P3", str(w), str(h), "255"]
-    got = np.array(tok[4:], np.int64).reshape(h, w, 3)
+    run_example("whitted", w, h, spp, out)
     ref, _, _ = ws.reference("example")
-    assert np.array_equal(got, pyoracle.tonemap(ref, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(out, w, h), pyoracle.tonemap(ref, 1.2).astype(np.int64))

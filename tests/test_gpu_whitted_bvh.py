@@ -3,52 +3,23 @@ in whitted.hip) against the restatement (tests/whitted_restatement.py, a linear 
 triangle): every frame bit for bit, every counter for equality, the schedule
 XRT_SCHED_WHITTED_BVH.  The scenes and the conditions they are chosen for are in
 tests/whitted_bvh_scenes.py and checked without a GPU in tests/test_whitted_bvh_restatement.py."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import pyoracle
 import whitted_bvh_scenes as wb
 import whitted_scenes as ws
+from gpu_checks import DATA_DIR, assert_frame, assert_same_bits, check_whitted_case, read_ppm, render_rc, run_example
 from xraytracer_amd import abi
 from xraytracer_amd.renderer import HipRenderer
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32),
-                          np.ascontiguousarray(b, np.float32).view(np.uint32))
-
-
-def first_diff(a, b):
-    d = np.argwhere(np.ascontiguousarray(a, np.float32).view(np.uint32) != np.ascontiguousarray(b, np.float32).view(np.uint32))
-    return [(tuple(int(x) for x in q), float(a[tuple(q)]), float(b[tuple(q)])) for q in d[:4]]
-
 
 def check_case(name, devices=None):
     """render wb.CASES[name] on the GPU with the flag and compare frame, counters and schedule
     with the restatement"""
-    _, w, h, spp, depth, kw = wb.CASES[name]
-    kw = dict(kw)
-    initial = ws.initial_image(w, h) if kw.pop("initial", False) else None
-    ref, cnt, per = wb.reference(name)
-    r = HipRenderer(spp, devices=devices)
-    try:
-        img = r.render(wb.scene(name), w, h, initial=initial, max_depth=depth, whitted_bvh=True, **kw)
-        st = r.stats
-        assert st.schedule == abi.XRT_SCHED_WHITTED_BVH
-        got = {k: int(getattr(st, k)) for k in ws.COUNTERS}
-        assert got == {k: int(cnt[k]) for k in ws.COUNTERS}
-        assert same_bits(img, ref), first_diff(img, ref)
-    finally:
-        r.close()
-    return img, cnt, per
+    return check_whitted_case(wb, name, abi.XRT_SCHED_WHITTED_BVH, devices=devices, whitted_bvh=True)
 
 
 # 1. two-level, glass: the small objects' LDS scan merged with the mesh's BVH walk
@@ -117,7 +88,8 @@ def test_timing_flag():
     r = HipRenderer(spp)
     try:
         img = r.render(wb.scene("glass"), w, h, max_depth=depth, whitted_bvh=True, timing=True)
-        assert r.stats.schedule == abi.XRT_SCHED_WHITTED_BVH and same_bits(img, ref)
+        assert r.stats.schedule == abi.XRT_SCHED_WHITTED_BVH
+        assert_frame(img, ref)
         assert r.stats.launches[abi.XRT_K_STEP] == 1 and r.stats.kernel_ms[abi.XRT_K_STEP] > 0.0
     finally:
         r.close()
@@ -135,26 +107,13 @@ def test_lds_scene_is_unchanged_by_the_flag():
         flagged = r.render(ws.scene("example"), w, h, max_depth=depth, whitted_bvh=True)
         assert r.stats.schedule == abi.XRT_SCHED_WHITTED
         assert {k: int(getattr(r.stats, k)) for k in ws.COUNTERS} == {k: int(cnt[k]) for k in ws.COUNTERS}
-        assert same_bits(flagged, plain) and same_bits(flagged, ref)
+        assert_same_bits(flagged, plain)
+        assert_frame(flagged, ref)
     finally:
         r.close()
 
 
 # 9. refusals
-def render_rc(scene, w, h, spp, **kw):
-    """xrt_render's status and message for a render that may be refused"""
-    r = HipRenderer(spp)
-    try:
-        r.upload(scene)
-        p = r.params(scene, w, h, **kw)
-        img = np.zeros((h, w, 3), np.float32)
-        st = abi.XrtStats()
-        rc = abi.lib().xrt_render(r.ctx, C.byref(p), abi.fptr(img), C.byref(st))
-        return rc, abi.lib().xrt_last_error(r.ctx).decode()
-    finally:
-        r.close()
-
-
 def test_glass_depth_limit_holds_with_the_flag():
     rc, msg = render_rc(wb.scene("glass"), 24, 18, 1, max_depth=abi.XRT_WHITTED_MAX_DEPTH + 1, whitted_bvh=True)
     assert rc == abi.XRT_ERR_UNSUPPORTED and "XRT_WHITTED_MAX_DEPTH" in msg
@@ -177,12 +136,7 @@ def test_scene_without_a_triangle_bvh_is_refused():
 def test_whitted_mesh_example_ppm(tmp_path):
     _, w, h, spp, _, _ = wb.CASES["glass"]
     out = tmp_path / "whitted_mesh.ppm"
-    env = dict(os.environ, XRT_DATA_DIR=os.path.join(ROOT, "xraytracer_amd", "data") + os.sep)
-    log = subprocess.run([os.path.join(ROOT, "examples", "bin", "whitted_mesh"), str(w), str(h), str(spp), str(out)],
-                         check=True, capture_output=True, text=True, env=env).stdout
+    log = run_example("whitted_mesh", w, h, spp, out, env={"XRT_DATA_DIR": DATA_DIR})
     assert f"(schedule {abi.XRT_SCHED_WHITTED_BVH})" in log
-    tok = out.read_text().split()
-    assert tok[:4] == ["P3", str(w), str(h), "255"]
-    got = np.array(tok[4:], np.int64).reshape(h, w, 3)
     ref, _, _ = wb.reference("glass")
-    assert np.array_equal(got, pyoracle.tonemap(ref, 1.2).astype(np.int64))
+    assert np.array_equal(read_ppm(out, w, h), pyoracle.tonemap(ref, 1.2).astype(np.int64))
