@@ -576,6 +576,13 @@ int xrt_test_fastdiv(xrt_ctx* ctx, uint32_t mode, float c, float rc, uint64_t* n
  * 1.3) over in[i] = {I.xyz, N.xyz}: out[i] = {reflect.xyz, refract.xyz, kr, normalize(reflect).xyz,
  * normalize(refract).xyz} (13 floats) */
 int xrt_test_whitted_math(xrt_ctx* ctx, const float* in, uint32_t n, float* out);
+/* The camera lists of the speculative merged schedule (k_camlist) for the uploaded scene and
+ * camera and p's image and row shard, as a render of p would build them, without its retirement
+ * of the empty pixels: out[4 s .. 4 s + 3] = {list bits 0-31, bits 32-63, the covering triangle
+ * or 0xffffffff, 0} of slot s — column s % width, row shard_index + shard_count * (s / width);
+ * the bits and the covering triangle count triangles in object order.  XRT_ERR_STATE unless the
+ * scene is a triangle scene of 1 to 64 triangles.  Nothing a later render reads is left changed. */
+int xrt_test_camlist(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """Scenes for the empty-pixel tests (tests/test_camlist_restatement.py on the CPU,
-tests/test_gpu_elide.py on the device) — a test helper, not a test file.
+tests/test_gpu_elide.py on the device) — a test helper, not a test file.  tests/camlist_scenes.py
+adds them, and scenes of its own built on `eye_scene` and `at`, to the camera-list tests.
 
 Every scene is a handful of triangles under GIIntegrator(3) with one area light, so the device
 renders it in the merged schedule.  `eye_scene` puts the camera at the origin looking down -z

@@ -9,10 +9,12 @@ and every counter (Scene::intersect calls, shadow rays, draws, rejects) equal to
 reference's sequential NormalRenderer::doRender (Src/renderer.cpp:29-81) as restated by the
 oracle.  The variant is the default (XRT_FLAG_NO_SPEC turns it off: same image, no speculative
 launch).  Cases force it on every launch (slots_per_wave=16, 8 or 4) and let the library mix
-it with the other layouts; cover launch boundaries (1-3 visits per launch: samples and
+it with the other layouts; cover launch boundaries (1-7 visits per launch: samples and
 pending shadow rays cross launches), depths 2-5, rejects with the in-place accumulate
-contract, the camera lists' covered / multi-triangle / empty pixels, and C2's own geometry
-as one row shard of an 8-GPU frame.
+contract, C2's own geometry as one row shard of an 8-GPU frame, and the flag that turns the
+variant off.  Every scene here is the Cornell box, and no case asserts which pixels took the
+camera lists' covering shortcut, their cull or a multi-triangle list: the lists themselves, and
+frames shown to hold each of those classes, are tests/test_gpu_camlist.py's.
 """
 import numpy as np
 import pytest

@@ -220,6 +220,7 @@ SIGNATURES = {
     "xrt_tonemap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint8)]),
     "xrt_test_whitted_math": (C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
     "xrt_test_fastdiv": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_uint64), u32p]),
+    "xrt_test_camlist": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
 }
 
 _lib = None

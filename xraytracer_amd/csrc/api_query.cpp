@@ -99,6 +99,28 @@ int xrt_test_whitted_math(xrt_ctx* c, const float* in, uint32_t n, float* out) {
     return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_whitted_math");
 }
 
+// the camera lists k_camlist builds for the render p describes (spec.hip), 4 words per slot
+int xrt_test_camlist(xrt_ctx* c, const xrt_render_params* p, uint32_t* out) {
+    c = first_device(c);
+    if (!c || !p || !out) return XRT_ERR_INVALID;
+    if (!c->has_scene || !c->has_camera) return set_err(c, XRT_ERR_STATE, "upload a scene and set a camera first");
+    if (c->base.scene_kind != SCN_TRI || c->base.n_tris < 1 || c->base.n_tris > 64)
+        return set_err(c, XRT_ERR_STATE, "xrt_test_camlist: the camera lists are built for a scene of 1 to 64 triangles");
+    if (p->width == 0 || p->height == 0 || p->shard_count == 0 || p->shard_index >= p->shard_count)
+        return set_err(c, XRT_ERR_INVALID, "bad image size or shard");
+    const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;
+    if (n == 0) return XRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->camlist, n * sizeof(uint4)))) return rc;
+    KParams P = render_params(c, p, n, nullptr);   // retire = 0: of the slots and the image nothing is touched
+    P.camlist = as<uint4>(c->camlist);
+    hipError_t e = launch_camlist(P, false, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, c->camlist.p, n * sizeof(uint4), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_camlist");
+}
+
 int xrt_test_trig(xrt_ctx* c, const float* x, uint32_t n, float* out) {
     c = first_device(c);
     if (!c || !x || !out) return XRT_ERR_INVALID;

@@ -76,6 +76,8 @@ __device__ __forceinline__ v3 qsel3(v3 v, int src_lane) {
 // larger on every ray of the cone, so it is never the (t, index) minimum.  When one triangle
 // is left and it covers the cone, every camera ray of the pixel hits it: `covering` is then
 // its index and the candidate rays need no test (the shading recomputes t, u, v anyway).
+// tests/camlist_restatement.py restates all of it operation by operation (change both together);
+// tests/test_gpu_camlist.py compares these lists with it word for word (xrt_test_camlist).
 //
 // retire (plan_render's elide: GIIntegrator, XRT_CAM_ELIDE): a pixel whose set is empty before
 // the covering cull — which cannot empty a set: the covering triangle stays — is finished here.

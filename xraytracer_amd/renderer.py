@@ -304,6 +304,17 @@ class HipRenderer:
                     "xrt_query")
         return out[:n]
 
+    def camlist(self, scene: SceneBundle, width: int, height: int, shard_index: int = 0, shard_count: int = 1):
+        """The camera lists the speculative merged schedule builds for the shard (xrt_test_camlist, a
+        device self-test): (slots, 4) uint32 in slot order — list bits 0-31, bits 32-63, the
+        covering triangle or 0xffffffff, 0."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, shard_index=shard_index, shard_count=shard_count)
+        out = np.zeros((len(range(shard_index, height, shard_count)) * width, 4), np.uint32)
+        self._check(self._lib.xrt_test_camlist(self.ctx, C.byref(p), abi.u32ptr(out)), "xrt_test_camlist")
+        return out
+
     def tonemap(self, width: int, height: int, gamma: float, device_ptr: int = 0) -> np.ndarray:
         """Image::gammaCorrection(gamma) + writePPM's 8-bit quantisation on the GPU, of the
         last render() (device_ptr 0) or of a device float3 buffer: (H, W, 3) uint8."""
