@@ -324,6 +324,45 @@ int  xrt_render_device(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_ou
 int  xrt_render_device_after(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_out, void* hip_stream,
                              xrt_stats* st);
 
+/* ---- a render with its per-pixel sample variance ---------------------------------------- */
+/* The frame of xrt_render and, beside it, the variance of each pixel's mean luminance: the
+ * plane xrt_denoise_var reads as `variance`.
+ *   rgb_out      [H][W][3]  exactly xrt_render's frame for the same p, bit for bit, the sign of
+ *                           a zero included
+ *   variance_out [H][W]     from the pixel's own samples, in IEEE float32, one rounding per
+ *                           operation, no FMA:
+ *       lum(r) = (0.2126f r.x + 0.7152f r.y) + 0.0722f r.z
+ *       s1 = s2 = +0
+ *       for the samples k = 0 .. spp - 1 in sample order, each sample r that Image::addPixel
+ *       accepts (not NaN / Inf / negative: the test the frame uses)
+ *           l  = lum(r)
+ *           s1 = s1 + l
+ *           s2 = s2 + l * l
+ *       n        = (float)spp
+ *       mean     = s1 / n
+ *       v        = s2 / n - mean * mean
+ *       v        = v > 0 ? v : +0
+ *       variance = v / (float)(spp - 1)
+ *     A rejected sample adds nothing and n stays spp, as for the frame.
+ * Pixels outside the shard are +0 in both planes.
+ * Refusals: XRT_ERR_INVALID for a NULL ctx, p, rgb_out or variance_out and for spp < 2 (one sample
+ * has no variance); XRT_ERR_UNSUPPORTED with XRT_FLAG_ACCUMULATE (the moments of the earlier
+ * calls' samples are unknown); and everything xrt_render refuses, the same way.
+ * Schedule: the six path integrators always run the wavefront schedule (XRT_SCHED_WAVEFRONT),
+ * WhittedIntegrator XRT_SCHED_WHITTED / XRT_SCHED_WHITTED_BVH as in xrt_render; the other schedule
+ * flags, slots_per_wave and visits_per_launch are checked as xrt_render checks them and have no
+ * effect.  XRT_FLAG_TIMING works.  Every xrt_stats field is what xrt_render reports for the same
+ * p with XRT_FLAG_WAVEFRONT set (the plane's kernel runs and is timed under XRT_K_FINISH).
+ * A multi-device context shards rows as for a render and assembles both planes on devices[0].
+ * After the call the context's last framebuffer — what xrt_tonemap and the filters read for a
+ * NULL colour — is this frame, for the device entry point too. */
+/* into caller-owned HOST memory; blocks until done */
+int  xrt_render_var(xrt_ctx* ctx, const xrt_render_params* p, float* rgb_out, float* variance_out, xrt_stats* st);
+/* into DEVICE pointers on this context's GPU (devices[0]); ordering as xrt_render_device_after:
+ * waits only for the work queued so far on hip_stream (NULL = the legacy default stream) */
+int  xrt_render_var_device(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_out, float* d_variance_out,
+                           void* hip_stream, xrt_stats* st);
+
 /* ---- first-hit guide buffers (AOVs) --------------------------------------------------- */
 /* Per-pixel guide planes for a denoiser or compositor, taken through the render's own camera
  * rays: sample k of pixel (row i, col j) takes words 2k, 2k + 1 of the pixel's stream (seed

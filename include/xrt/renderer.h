@@ -74,6 +74,12 @@ public:
     // Errors are reported like the reference reports them (logged; the image is left as
     // rendered so far); lastStatus()/lastError() expose them to callers that care.
     void render(const Scene& scene, Sampler::SamplerType st, Image& image) const override;
+    // render() over a zero Image — `image`'s earlier contents are replaced, not added to — and,
+    // beside the frame, the variance of each pixel's mean luminance from the pixel's own samples
+    // (xrt.h, xrt_render_var; n_samples must be at least 2): `variance` is resized to width *
+    // height in Image::pixels order.  It is what denoiseVar takes as variance_in.  Errors as
+    // render() reports them.
+    void renderVariance(const Scene& scene, Sampler::SamplerType st, Image& image, std::vector<float>& variance) const;
     // The guide buffers of the frame render() would make of `scene` with this camera and
     // n_samples (the integrator is not consulted); errors as render() reports them.
     void renderGuides(const Scene& scene, GuideImages& guides) const;
@@ -86,6 +92,11 @@ public:
     // the last pass.
     void denoiseVar(Image& image, const GuideImages& guides, const DenoiseVarSettings& settings = {},
                     std::vector<float>* variance_out = nullptr) const;
+    // ... with the caller's variance of each pixel's luminance, renderVariance's for instance
+    // (width * height elements, finite and >= 0), in place of the estimate; variance_out may be
+    // variance_in's vector.
+    void denoiseVar(Image& image, const GuideImages& guides, const std::vector<float>& variance_in,
+                    const DenoiseVarSettings& settings = {}, std::vector<float>* variance_out = nullptr) const;
     int lastStatus() const { return m_status; }
     const std::string& lastError() const { return m_error; }
     const xrt_stats& lastStats() const { return m_stats; }
@@ -98,6 +109,12 @@ private:
     // the start of denoise() / denoiseVar() (`who`): the guide planes of `guides` that have a size, as
     // the filters read them, and the context; false after fail()
     bool filterInputs(const char* who, const Image& image, const GuideImages& guides, xrt_aov_buffers& in) const;
+    // both denoiseVar()s: variance_in null = estimated from the image
+    void filterVar(Image& image, const GuideImages& guides, const float* variance_in, const DenoiseVarSettings& settings,
+                   std::vector<float>* variance_out) const;
+    // the start of render() / renderVariance(): scene, camera and medium uploaded, and p for `image`
+    // with this integrator and n_samples; false after a failure (m_status, m_error set)
+    bool renderInputs(const Scene& scene, const Image& image, xrt_render_params& p) const;
     const uint32_t n_samples;
     int m_device;
     std::vector<int> m_devices;   // empty: one GPU (m_device)

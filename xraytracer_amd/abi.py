@@ -180,6 +180,9 @@ SIGNATURES = {
     "xrt_render_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.POINTER(XrtStats)]),
     "xrt_render_device_after": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.c_void_p,
                                           C.POINTER(XrtStats)]),
+    "xrt_render_var": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), f32p, f32p, C.POINTER(XrtStats)]),
+    "xrt_render_var_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(XrtStats)]),
     "xrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.POINTER(XrtStats)]),
     "xrt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.c_void_p,
                                         C.POINTER(XrtStats)]),

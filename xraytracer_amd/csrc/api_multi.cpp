@@ -80,22 +80,29 @@ xrt_stats sum_stats(const std::vector<xrt_stats>& S) {
 }
 
 int render_multi(xrt_ctx* m, const xrt_render_params* p, float* d_out, float* h_io, xrt_stats* st, int wait,
-                 hipStream_t wait_stream) {
+                 hipStream_t wait_stream, float* d_var) {
     const auto t_start = std::chrono::steady_clock::now();
     if (!p) return set_err(m, XRT_ERR_INVALID, "null params");
     if (p->width == 0 || p->height == 0 || p->shard_count == 0 || p->shard_index >= p->shard_count)
         return set_err(m, XRT_ERR_INVALID, "bad image size or shard");
     const uint32_t n = (uint32_t)m->subs.size();
     const size_t npix = (size_t)p->width * p->height, bytes = npix * 3 * sizeof(float);
-    const bool acc = (p->flags & XRT_FLAG_ACCUMULATE) != 0;
+    const bool acc = (p->flags & XRT_FLAG_ACCUMULATE) != 0 && !d_var;   // a variance render refuses it
     xrt_ctx* s0 = m->subs[0];
     int rc = order_after(s0, wait, wait_stream, true);
     if (rc) return set_err(m, rc, s0->err);
     // every device renders into its own framebuffer; device 0 directly into the output
-    std::vector<void*> fbs(n, nullptr);
+    // ... and a variance render's plane likewise: device 0 into d_var
+    std::vector<void*> fbs(n, nullptr), vars(n, nullptr);
     for (uint32_t i = 0; i < n; ++i) {
         xrt_ctx* s = m->subs[i];
         HIPCHK(m, hipSetDevice(s->device));
+        if (d_var && i == 0) {
+            vars[0] = d_var;
+        } else if (d_var) {
+            if ((rc = ensure(s, s->var, npix * sizeof(float)))) return multi_fail(m, s, rc, "variance plane");
+            vars[i] = s->var.p;
+        }
         if (i == 0 && d_out) {
             fbs[0] = d_out;
         } else {
@@ -112,9 +119,10 @@ int render_multi(xrt_ctx* m, const xrt_render_params* p, float* d_out, float* h_
     std::vector<xrt_stats> S(n);
     if ((rc = fan_out_rows(m, p, "render",
                            [&](uint32_t i, const xrt_render_params* q) {
-                               return render_impl(m->subs[i], q, static_cast<float*>(fbs[i]), nullptr, &S[i]);
+                               return render_impl(m->subs[i], q, static_cast<float*>(fbs[i]), nullptr, &S[i], 0, nullptr,
+                                                  static_cast<float*>(vars[i]));
                            })) ||
-        (rc = gather_rows(m, p, {RowPlane{fbs, 3 * sizeof(float)}})))
+        (rc = gather_rows(m, p, {RowPlane{fbs, 3 * sizeof(float)}, RowPlane{vars, sizeof(float)}})))
         return rc;
     if (h_io) HIPCHK(m, hipMemcpy(h_io, fbs[0], bytes, hipMemcpyDeviceToHost));
     if (st) {

@@ -103,8 +103,17 @@ int check_render(xrt_ctx* c, const xrt_render_params* p) {
     return XRT_OK;
 }
 
+// what a variance render refuses beyond check_render
+int check_render_var(xrt_ctx* c, const xrt_render_params* p) {
+    if (p->spp < 2) return set_err(c, XRT_ERR_INVALID, "xrt_render_var: spp must be at least 2 (one sample has no variance)");
+    if (p->flags & XRT_FLAG_ACCUMULATE)
+        return set_err(c, XRT_ERR_UNSUPPORTED,
+                       "xrt_render_var: XRT_FLAG_ACCUMULATE (the moments of the earlier calls' samples are unknown)");
+    return XRT_OK;
+}
+
 // a shard that owns no rows (shard_index >= height): an all-zero framebuffer
-int render_empty_shard(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st,
+int render_empty_shard(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, float* d_var, xrt_stats* st,
                        std::chrono::steady_clock::time_point t_start) {
     const size_t npix = (size_t)p->width * p->height;
     int rc;
@@ -112,6 +121,7 @@ int render_empty_shard(xrt_ctx* c, const xrt_render_params* p, float* d_out, flo
     float* fb0 = d_out ? d_out : as<float>(c->fb);
     if (p->flags & XRT_FLAG_ACCUMULATE) return XRT_OK;   // nothing owned, nothing touched
     HIPCHK(c, hipMemsetAsync(fb0, 0, npix * 3 * sizeof(float), c->stream));
+    if (d_var) HIPCHK(c, hipMemsetAsync(d_var, 0, npix * sizeof(float), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h_out) HIPCHK(c, hipMemcpy(h_out, fb0, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (st) {
@@ -223,10 +233,14 @@ struct RenderPlan {
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
     uint64_t cap_iters;                            // loop iterations at most
+    // a variance render (xrt_render_var): the slots' {s1, s2} records, which select the moments
+    // builds of k_shade / k_whitted / k_whitted_bvh; null for a plain render
+    float2* mom;
 };
 
-RenderPlan plan_render(const KParams& P, const xrt_render_params* p) {
+RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom) {
     RenderPlan R{};
+    R.mom = mom;
     const size_t n = P.n_slots;
     R.volumetric = p->integrator == XRT_INTEGRATOR_VPT || p->integrator == XRT_INTEGRATOR_VPT_NEE;
     // The fused k_step (scene resident in LDS, step_visits path segments per slot per launch,
@@ -360,8 +374,8 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
         // (zeroed with them)
         uint32_t* work = reinterpret_cast<uint32_t*>(P.stats + kStatsWork);
         const hipError_t e = T.launch(XRT_K_STEP, [&] {
-            return R.whitted_bvh ? launch_whitted_bvh(P, work, c->stream)
-                   : R.whitted   ? launch_whitted(P, work, c->stream)
+            return R.whitted_bvh ? launch_whitted_bvh(P, work, c->stream, R.mom)
+                   : R.whitted   ? launch_whitted(P, work, c->stream, R.mom)
                                  : launch_pixel(P, work, c->stream);
         });
         if (e != hipSuccess) return hip_err(c, e, R.whitted_bvh ? "k_whitted_bvh" : R.whitted ? "k_whitted" : "k_pixel");
@@ -431,7 +445,8 @@ int run_wavefront(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveL
     for (it = 0; it < R.cap_iters && !poll.done; ++it) {
         const int cur = (int)(it & 1), nxt = cur ^ 1;
         hipError_t e = T.launch(XRT_K_SHADE, [&] {
-            return launch_shade(P, L.list[cur], L.counts(cur), L.list[nxt], L.counts(nxt), L.req(1), blocks, c->stream);
+            return launch_shade(P, L.list[cur], L.counts(cur), L.list[nxt], L.counts(nxt), L.req(1), blocks, c->stream,
+                                R.mom);
         });
         if (e != hipSuccess) return hip_err(c, e, "k_shade");
         e = T.launch(XRT_K_TRACE, [&] {
@@ -472,16 +487,29 @@ int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
 }  // namespace
 
 int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st, int wait,
-                hipStream_t wait_stream) {
+                hipStream_t wait_stream, float* d_var) {
     const auto t_start = std::chrono::steady_clock::now();
     int rc = check_render(c, p);
-    if (rc || (rc = order_after(c, wait, wait_stream, false))) return rc;
+    if (rc) return rc;
+    // A variance render is this render with its plan forced to the wavefront schedule (Whitted has
+    // one schedule anyway): no other schedule flag and no launch geometry reaches the plan.
+    xrt_render_params forced;
+    if (d_var) {
+        if ((rc = check_render_var(c, p))) return rc;
+        forced = *p;
+        forced.flags = (p->flags & (XRT_FLAG_TIMING | XRT_FLAG_WHITTED_BVH)) | XRT_FLAG_WAVEFRONT;
+        forced.slots_per_wave = forced.visits_per_launch = 0;
+        p = &forced;
+    }
+    if ((rc = order_after(c, wait, wait_stream, false))) return rc;
     const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;
     const size_t npix = (size_t)p->width * p->height;
-    if (n == 0) return render_empty_shard(c, p, d_out, h_out, st, t_start);
+    if (n == 0) return render_empty_shard(c, p, d_out, h_out, d_var, st, t_start);
 
     // buffers, parameters, plan
-    if ((rc = grow_slots(c, n)) || (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float))))) return rc;
+    if ((rc = grow_slots(c, n)) || (!d_out && (rc = ensure(c, c->fb, npix * 3 * sizeof(float)))) ||
+        (d_var && (rc = ensure(c, c->mom, n * sizeof(float2)))))
+        return rc;
     float* fb = d_out ? d_out : as<float>(c->fb);   // the caller's device image, or the context's own
     KParams P = render_params(c, p, n, fb);
     if (p->integrator == XRT_INTEGRATOR_WHITTED && !use_whitted(P)) {
@@ -493,7 +521,7 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
                            "WhittedIntegrator with XRT_FLAG_WHITTED_BVH: the scene neither fits the LDS-resident scene "
                            "carve nor has a triangle BVH (a large sphere-only or mixed scene)");
     }
-    const RenderPlan R = plan_render(P, p);
+    const RenderPlan R = plan_render(P, p, d_var ? as<float2>(c->mom) : nullptr);
     if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
     P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep;
     const size_t lcap = (size_t)P.n_part * P.part_cap;
@@ -514,6 +542,7 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
         HIPCHK(c, hipMemsetAsync(fb, 0, npix * 3 * sizeof(float), c->stream));
     else if (h_out)   // the caller's Image is the accumulator (Src/renderer.cpp:75)
         HIPCHK(c, hipMemcpyAsync(fb, h_out, npix * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (d_var) HIPCHK(c, hipMemsetAsync(d_var, 0, npix * sizeof(float), c->stream));   // outside the shard: +0
     HIPCHK(c, hipMemsetAsync(P.stats, 0, 512, c->stream));
     if ((rc = seed_paths(c, P, R, L, T))) return rc;
 
@@ -522,7 +551,10 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     uint64_t it = 0;
     if (!R.pixel && (rc = R.fused ? run_fused(c, P, R, L, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it)))
         return rc;
-    HIPCHK(c, T.launch(XRT_K_FINISH, [&] { return launch_finish(P, c->stream); }));
+    HIPCHK(c, T.launch(XRT_K_FINISH, [&] {   // a variance render's plane counts as part of the finish
+        const hipError_t e = launch_finish(P, c->stream);
+        return e != hipSuccess || !R.mom ? e : launch_finish_var(P, R.mom, d_var, c->stream);
+    }));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!R.pixel && !poll.done) {
         // the iteration cap was reached without observing an empty list: verify
@@ -572,6 +604,41 @@ int xrt_render_device_after(xrt_ctx* c, const xrt_render_params* p, float* d_rgb
     if (!d_rgb_out) return set_err(c, XRT_ERR_INVALID, "null output");
     if (c && !c->subs.empty()) return render_multi(c, p, d_rgb_out, nullptr, st, 2, (hipStream_t)hip_stream);
     return render_impl(c, p, d_rgb_out, nullptr, st, 2, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------- variance render ----
+// xrt_render_var / xrt_render_var_device: render_impl (render_multi) with a variance plane.  The
+// plane is rendered into device memory — the context's own for the host entry point — and the
+// frame is left in the context's framebuffer, where xrt_tonemap and the filters read it.
+static int render_var(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, float* d_var, float* h_var,
+                      xrt_stats* st, int wait, hipStream_t wait_stream) {
+    if (!c || !p || !(d_out || h_out) || !(d_var || h_var)) return set_err(c, XRT_ERR_INVALID, "xrt_render_var: null argument");
+    xrt_ctx* c0 = first_device(c);
+    const size_t npix = (size_t)p->width * p->height;
+    int rc;
+    if (!d_var) {
+        HIPCHK(c, hipSetDevice(c0->device));
+        if ((rc = ensure(c0, c0->var, npix * sizeof(float)))) return c0 == c ? rc : multi_fail(c, c0, rc, "variance plane");
+        d_var = as<float>(c0->var);
+    }
+    rc = !c->subs.empty() ? render_multi(c, p, d_out, h_out, st, wait, wait_stream, d_var)
+                          : render_impl(c, p, d_out, h_out, st, wait, wait_stream, d_var);
+    if (rc) return rc;
+    if (h_var) HIPCHK(c, hipMemcpy(h_var, d_var, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (d_out) {   // the caller's image: the context's framebuffer gets a copy
+        if ((rc = ensure(c0, c0->fb, npix * 3 * sizeof(float)))) return c0 == c ? rc : multi_fail(c, c0, rc, "framebuffer");
+        HIPCHK(c, hipMemcpy(c0->fb.p, d_out, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice));
+    }
+    return XRT_OK;
+}
+
+int xrt_render_var(xrt_ctx* c, const xrt_render_params* p, float* rgb_out, float* variance_out, xrt_stats* st) {
+    return render_var(c, p, nullptr, rgb_out, nullptr, variance_out, st, 0, nullptr);
+}
+
+int xrt_render_var_device(xrt_ctx* c, const xrt_render_params* p, float* d_rgb_out, float* d_variance_out,
+                          void* hip_stream, xrt_stats* st) {
+    return render_var(c, p, d_rgb_out, nullptr, d_variance_out, nullptr, st, 2, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

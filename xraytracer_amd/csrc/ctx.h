@@ -43,6 +43,9 @@ struct xrt_ctx {
     xrt::DevBuf ray_o, ray_d, thr, rad, thr_prev, hit, hit2, hit3, sh_o, sh_d, sh_c, med, med2, nee;
     xrt::DevBuf state, sample_k, depth, occ, rng_c, rng_g, ring, c_seg, c_shadow, c_rej, c_stall, lists, deep, camlist;
     xrt::DevBuf counts, stats, fb, scratch, kparams;
+    // xrt_render_var: per slot the {s1, s2} luminance moments (float2), and the context's own
+    // variance plane (host output, sub-contexts of a multi render)
+    xrt::DevBuf mom, var;
     uint32_t* h_poll = nullptr;  // pinned: LivePoll's 8 slots of kMaxParts counts
     std::vector<hipEvent_t> events;   // LaunchTimer's pairs
     hipEvent_t poll_ev[8] = {};  // LivePoll's events (created once)
@@ -147,9 +150,10 @@ struct LiveLists {
 int setup_deep(xrt_ctx* c, KParams& P);   // the two-level trace queues (KParams::deep)
 int grow_slots(xrt_ctx* c, size_t n);
 KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* fb);
-// wait, wait_stream: order_after's
+// wait, wait_stream: order_after's.  d_var: a variance render (xrt_render_var) — the device plane
+// [height][width] that gets the variance of each pixel's mean luminance; null: a plain render
 int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st, int wait = 0,
-                hipStream_t wait_stream = nullptr);
+                hipStream_t wait_stream = nullptr, float* d_var = nullptr);
 
 // ---- api_multi.cpp: the multi-GPU context
 // its first device, where frames and planes are assembled (a single-device context: itself)
@@ -184,9 +188,10 @@ int gather_rows(xrt_ctx* m, const xrt_render_params* p, const std::vector<RowPla
 
 xrt_stats sum_stats(const std::vector<xrt_stats>& S);   // the devices' stats as one (wall_ms: device 0's)
 
-// d_out: the caller's device image on subs[0]'s GPU (or null: host image h_io)
+// d_out: the caller's device image on subs[0]'s GPU (or null: host image h_io); d_var: render_impl's,
+// on subs[0]'s GPU
 int render_multi(xrt_ctx* m, const xrt_render_params* p, float* d_out, float* h_io, xrt_stats* st, int wait,
-                 hipStream_t wait_stream);
+                 hipStream_t wait_stream, float* d_var = nullptr);
 
 }  // namespace xrt
 

@@ -1,6 +1,6 @@
 // frame.hip — the kernels around a frame's path work, whatever the schedule: k_seed (the
 // per-pixel RNG streams and the first slot list), k_finish (the division by the sample count
-// and the counter reduction) and k_tonemap (gamma and 8-bit quantisation), with their launchers.
+// and the counter reduction), k_finish_var (a variance render's plane) and k_tonemap (gamma and 8-bit quantisation), with their launchers.
 #include "launch.h"
 #include "path_common.h"
 
@@ -94,6 +94,21 @@ __global__ __launch_bounds__(kBlock) void k_finish(KParams P) {
     }
 }
 
+// ============================================================== k_finish_var ====
+// A variance render's plane (xrt_render_var, include/xrt.h) from the slots' {s1, s2} records: the
+// variance of the pixel's mean luminance, one rounding per operation.
+__global__ __launch_bounds__(kBlock) void k_finish_var(KParams P, const float2* __restrict__ mom, float* __restrict__ var) {
+    const float n = (float)P.spp;
+    for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < P.n_slots; s += gridDim.x * kBlock) {
+        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const float2 m = mom[s];
+        const float mean = m.x / n;
+        float v = m.y / n - mean * mean;
+        v = v > 0.0f ? v : 0.0f;
+        var[(size_t)col + (size_t)P.width * row] = v / (float)(P.spp - 1u);
+    }
+}
+
 // ===================================================================== output ====
 // Image::gammaCorrection (Src/image.h:80-90: pow(c, 1.0f / gamma) per channel) followed by
 // writePPM's quantisation (:92-114: std::clamp(static_cast<uint32_t>(255.0f * c), 0u, 255u)),
@@ -118,6 +133,12 @@ hipError_t launch_seed(const KParams& P, uint32_t* list, uint32_t* count, uint32
 hipError_t launch_finish(const KParams& P, hipStream_t st) {
     const uint32_t blocks = std::min<uint32_t>((P.n_slots + kBlock - 1) / kBlock, 2048u);
     hipLaunchKernelGGL(k_finish, dim3(blocks), dim3(kBlock), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_finish_var(const KParams& P, const float2* mom, float* var, hipStream_t st) {
+    const uint32_t blocks = std::min<uint32_t>((P.n_slots + kBlock - 1) / kBlock, 2048u);
+    hipLaunchKernelGGL(k_finish_var, dim3(blocks), dim3(kBlock), 0, st, P, mom, var);
     return hipGetLastError();
 }
 

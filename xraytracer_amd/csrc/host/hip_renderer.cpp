@@ -116,6 +116,18 @@ void HipRenderer::denoise(Image& image, const GuideImages& g, const DenoiseSetti
 }
 
 void HipRenderer::denoiseVar(Image& image, const GuideImages& g, const DenoiseVarSettings& s, std::vector<float>* variance_out) const {
+    filterVar(image, g, nullptr, s, variance_out);
+}
+
+void HipRenderer::denoiseVar(Image& image, const GuideImages& g, const std::vector<float>& variance_in, const DenoiseVarSettings& s,
+                             std::vector<float>* variance_out) const {
+    if (variance_in.size() != (size_t)image.getWidth() * image.getHeight())
+        return fail(XRT_ERR_INVALID, "denoiseVar: variance_in must have width * height elements");
+    filterVar(image, g, variance_in.data(), s, variance_out);
+}
+
+void HipRenderer::filterVar(Image& image, const GuideImages& g, const float* variance_in, const DenoiseVarSettings& s,
+                            std::vector<float>* variance_out) const {
     xrt_aov_buffers in;
     if (!filterInputs("denoiseVar", image, g, in)) return;
     xrt_denoise_var_params p;
@@ -124,22 +136,39 @@ void HipRenderer::denoiseVar(Image& image, const GuideImages& g, const DenoiseVa
     p.sigma_luminance = s.sigma_luminance, p.sigma_normal = s.sigma_normal, p.sigma_depth = s.sigma_depth;
     p.sigma_albedo = s.sigma_albedo, p.variance_radius = s.variance_radius;
     p.flags = (s.timing ? XRT_DENOISE_TIMING : 0u) | (s.tile ? 0u : XRT_DENOISE_NO_TILE);
-    if (variance_out) variance_out->assign((size_t)p.width * p.height, 0.0f);
-    const int rc = xrt_denoise_var(m_ctx, &p, image.data(), nullptr, &in, image.data(), variance_out ? variance_out->data() : nullptr,
-                                   &m_denoise_stats);
+    // variance_out may be variance_in's vector: the filter works in place
+    if (variance_out && variance_out->data() != variance_in) variance_out->assign((size_t)p.width * p.height, 0.0f);
+    const int rc = xrt_denoise_var(m_ctx, &p, image.data(), variance_in, &in, image.data(),
+                                   variance_out ? variance_out->data() : nullptr, &m_denoise_stats);
     if (rc != XRT_OK) fail(rc, std::string("xrt_denoise_var: ") + xrt_last_error(m_ctx));
 }
 
 void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image) const {
+    xrt_render_params p;
+    if (!renderInputs(scene, image, p)) return;
+    p.flags |= XRT_FLAG_ACCUMULATE;   // samples are added to the Image in place (Src/renderer.cpp:75, 98)
+    const int rc = xrt_render(m_ctx, &p, image.data(), &m_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_render: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::renderVariance(const Scene& scene, Sampler::SamplerType, Image& image, std::vector<float>& variance) const {
+    xrt_render_params p;
+    variance.assign((size_t)image.getWidth() * image.getHeight(), 0.0f);
+    if (!renderInputs(scene, image, p)) return;
+    const int rc = xrt_render_var(m_ctx, &p, image.data(), variance.data(), &m_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_render_var: ") + xrt_last_error(m_ctx));
+}
+
+bool HipRenderer::renderInputs(const Scene& scene, const Image& image, xrt_render_params& p) const {
     auto fail = [&](int rc, const char* what) {
         m_status = rc;
         m_error = std::string(what) + ": " + (m_ctx ? xrt_last_error(m_ctx) : xrt_last_error(nullptr));
         std::fprintf(stderr, "[HipRenderer] %s\n", m_error.c_str());
+        return false;
     };
     int rc = prepare(scene);
-    if (rc != XRT_OK) return;
+    if (rc != XRT_OK) return false;
 
-    xrt_render_params p;
     std::memset(&p, 0, sizeof(p));
     switch (integrator->kind()) {
         case Integrator::Kind::GI: p.integrator = XRT_INTEGRATOR_GI; break;
@@ -205,8 +234,7 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
     p.spp = n_samples;
     p.shard_index = 0;
     p.shard_count = 1;
-    p.flags = XRT_FLAG_ACCUMULATE;   // samples are added to the Image in place (Src/renderer.cpp:75, 98)
     // the reference's Whitted loop runs over any Scene: take the BVH schedule when LDS is too small
     if (p.integrator == XRT_INTEGRATOR_WHITTED) p.flags |= XRT_FLAG_WHITTED_BVH;
-    if ((rc = xrt_render(m_ctx, &p, image.data(), &m_stats)) != XRT_OK) return fail(rc, "xrt_render");
+    return true;
 }

@@ -65,6 +65,9 @@ hipError_t persistent_blocks(K kernel, int block, size_t lds, uint32_t n_slots, 
 hipError_t launch_seed(const KParams& P, uint32_t* list, uint32_t* count, uint32_t* count_other,
                        uint32_t* req_count, hipStream_t st);
 hipError_t launch_finish(const KParams& P, hipStream_t st);
+// a variance render's plane: the slots' {s1, s2} records (k_shade / k_whitted with a `mom`) into
+// var [height][width], the shard's pixels only (xrt_render_var's last five operations)
+hipError_t launch_finish_var(const KParams& P, const float2* mom, float* var, hipStream_t st);
 // Image::gammaCorrection + writePPM quantisation of n floats into n bytes
 hipError_t launch_tonemap(const float* rgb, uint32_t n, float inv_gamma, uint8_t* out, hipStream_t st);
 
@@ -81,8 +84,10 @@ hipError_t launch_query(const KParams& P, const float* rays, const float* tmax, 
                         uint32_t* count, uint32_t* zero, xrt_hit* out, hipStream_t st);
 
 // ---------------------------------------------------------------------- shade.hip ----
+// mom: a variance render's per-slot {s1, s2} records (n_slots of them; the moments build of
+// k_shade), null for a plain render
 hipError_t launch_shade(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* out,
-                        uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st);
+                        uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st, float2* mom = nullptr);
 
 // ----------------------------------------------------------------------- step.hip ----
 // fused schedule (k_step): LDS bytes it needs for this scene, 0 = scene too large for it
@@ -149,13 +154,14 @@ hipError_t launch_pixel(const KParams& P, uint32_t* work, hipStream_t st);
 // pixel counter at `work`)
 bool use_whitted(const KParams& P);
 size_t whit_lds_bytes(const KParams& P);
-hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st);
+// mom: as launch_shade's
+hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st, float2* mom = nullptr);
 // ... and triangle scenes beyond it that have the triangle BVH (one- and two-level scenes):
 // k_whitted_bvh, the same loop tracing through the BVH and the small objects' LDS copy
 // (XRT_FLAG_WHITTED_BVH; same contract)
 bool use_whitted_bvh(const KParams& P);
 size_t whit_bvh_lds_bytes(const KParams& P);
-hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st);
+hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st, float2* mom = nullptr);
 // k_whitted's reflect / refract / fresnel / normalize over n inputs {I, N}: 13 floats each
 hipError_t launch_test_whitted(const float* in, uint32_t n, float* out, hipStream_t st);
 

@@ -639,6 +639,10 @@ __device__ __forceinline__ bool radiance_invalid(v3 r) {
            __builtin_isinf(r.y) || __builtin_isinf(r.z) || r.x < 0.0f || r.y < 0.0f || r.z < 0.0f;
 }
 
+// An accepted sample's luminance, the value whose moments a variance render sums (xrt_render_var;
+// the weights xrt_denoise_var reads its colour stop with, in its order of operations)
+__device__ __forceinline__ float luminance(v3 r) { return (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z; }
+
 // Russian roulette past depth 0 (Src/integrator.h:148-155, 224-231, 432-439, 508-515): false =
 // the path ends here; else throughput / Vec3f(p).  (k_shade and k_step hold it open-coded, see
 // there; k_step's volumetric integrators with the quotient through div3s: one division for an

@@ -20,10 +20,18 @@
 namespace xrt {
 
 // =================================================================== k_shade ====
-template <int SCN, int INTEG>
+// MOM (a variance render, xrt_render_var): the sample a slot finishes also adds its luminance l and
+// l * l to the slot's record mom[s] = {s1, s2}, which the slot's very first visit zeroes (k_finish_var,
+// frame.hip, turns the records into the variance plane).  The records take the place of req_count,
+// which k_shade does not read: a member more in KParams or an argument more would move the
+// arguments behind it, the hidden ones included, and with them instructions of every build.
+template <int SCN, int INTEG, bool MOM = false>
 __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, const uint32_t* __restrict__ list,
                                                    const uint32_t* __restrict__ count, uint32_t* __restrict__ out,
-                                                   uint32_t* out_count, uint32_t* req_count) {
+                                                   uint32_t* out_count,
+                                                   std::conditional_t<MOM, float2*, uint32_t*> req_count_or_mom) {
+    float2* mom = nullptr;
+    if constexpr (MOM) mom = req_count_or_mom;
     __shared__ __attribute__((aligned(16))) uint32_t rbuf[kBlock / 64][kMT];   // wave_refill staging
     const PartIter it = part_iter(P, count, kBlock);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -285,6 +293,12 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
                         const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
                         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
                         px[0] = px[0] + r.x, px[1] = px[1] + r.y, px[2] = px[2] + r.z;
+                        if (MOM) {   // s1 = s1 + l, s2 = s2 + l * l (include/xrt.h, xrt_render_var)
+                            const float l = luminance(r);
+                            float2 m = mom[s];
+                            m.x = m.x + l, m.y = m.y + l * l;
+                            mom[s] = m;
+                        }
                     }
                     ++k;
                 }
@@ -312,6 +326,7 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
             }
             if (st & ST_REGEN) {   // very first sample of the slot
                 st &= ~ST_REGEN;
+                if (MOM) mom[s] = make_float2(0.0f, 0.0f);
                 const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
                 const float u = div_w(P, (float)(int)col + rng.next());
                 const float v = div_h(P, (float)(int)row + rng.next());
@@ -348,15 +363,19 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
         wave_append(valid && !(st & ST_DONE), s, out + it.p * P.part_cap, out_count + it.p, lane);
         wave_refill(P, want_req && !(st & ST_DONE), s, g, lane, rbuf[tid >> 6]);
     }
-    (void)req_count;
+    (void)req_count_or_mom;
 }
 
 hipError_t launch_shade(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* out,
-                        uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st) {
+                        uint32_t* out_count, uint32_t* req_count, uint32_t blocks, hipStream_t st, float2* mom) {
     return with_scene_kind(P.scene_kind, [&](auto scn) {
         return with_integrator(P.integrator, [&](auto integ) {
-            hipLaunchKernelGGL((k_shade<decltype(scn)::value, decltype(integ)::value>), dim3(blocks), dim3(kBlock), 0, st,
-                               P, list, count, out, out_count, req_count);
+            if (mom)
+                hipLaunchKernelGGL((k_shade<decltype(scn)::value, decltype(integ)::value, true>), dim3(blocks), dim3(kBlock),
+                                   0, st, P, list, count, out, out_count, mom);
+            else
+                hipLaunchKernelGGL((k_shade<decltype(scn)::value, decltype(integ)::value>), dim3(blocks), dim3(kBlock), 0,
+                                   st, P, list, count, out, out_count, req_count);
             return hipGetLastError();
         });
     });

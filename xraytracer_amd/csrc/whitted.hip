@@ -175,9 +175,12 @@ __device__ v3 whit_integrate(const KParams& P, const TR& T, v3 ro, v3 rd, WhitCo
 // One wave's share of the shard: pixels from the counter at `work` until it runs out, the
 // pixel's stream in the wave's LDS slice st (kMT words, then the ordered-sum buffer), the
 // samples' ray trees through the trace policy T.  Both kernels below are this loop.
-template <typename TR>
+// MOM (a variance render, xrt_render_var): the accepted samples' luminance l and l * l go through
+// the same ordered sum, after the window's radiances, into two more running sums — lane 0 holds s1,
+// lane 1 s2 — and the pixel's record mom[s] = {s1, s2} is written for k_finish_var (frame.hip).
+template <bool MOM, typename TR>
 __device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint32_t* st, uint32_t* __restrict__ work,
-                                            int lane) {
+                                            int lane, float2* mom) {
     float* sum = reinterpret_cast<float*>(st + kMT);
     unsigned long long w_rays = 0, w_cut = 0, w_refr = 0, w_tir = 0;   // lane totals over this wave's pixels
     for (;;) {
@@ -198,6 +201,7 @@ __device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint3
         float acc = lane < 3 ? px[lane] : 0.0f;   // lane c < 3: channel c of the running sum
         uint32_t g = kMT;                         // x[0 .. g) generated; sample k draws x[kMT + 2k], x[kMT + 2k + 1]
         uint32_t nrej = 0;
+        float macc = 0.0f;                        // MOM: lane 0 the running s1, lane 1 the running s2
         WhitCount C;
         for (uint32_t k0 = 0; k0 < P.spp; k0 += 64u) {
             const uint32_t span = min(64u, P.spp - k0);
@@ -221,8 +225,13 @@ __device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint3
             const uint64_t vm = __ballot(act && !radiance_invalid(r));
             nrej += span - (uint32_t)__builtin_popcountll(vm);
             pix_add_in_order(sum, lane, acc, vm, r);
+            if (MOM) {
+                const float l = luminance(r);
+                pix_add_in_order(sum, lane, macc, vm, mk(l, l * l, 0.0f));
+            }
         }
         if (lane < 3) px[lane] = acc;
+        if (MOM && lane < 2) reinterpret_cast<float*>(mom + s)[lane] = macc;
         // the pixel's counters, as the per-slot schedules leave them for k_finish: its
         // Scene::intersect and Scene::occluded calls, its rejects, the stream cursor (two words
         // per sample) and the twists a std::mt19937 makes to produce that many words
@@ -251,8 +260,8 @@ __device__ __forceinline__ void whit_pixels(const KParams& P, const TR& T, uint3
     }
 }
 
-template <int SCN>
-__global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __restrict__ work) {
+template <int SCN, bool MOM = false>
+__global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __restrict__ work, float2* mom) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_whit[];
     char* lb = reinterpret_cast<char*>(lds_whit);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -260,7 +269,7 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
     uint32_t* st = reinterpret_cast<uint32_t*>(lb + whit_wave_off(P) + (tid >> 6) * kWhitWaveLds);
     __syncthreads();
     const WhitLds<SCN> T{P, L, L.obj};
-    whit_pixels(P, T, st, work, lane);
+    whit_pixels<MOM>(P, T, st, work, lane, mom);
 }
 
 // ------------------------------------------------------------ scenes beyond LDS ----
@@ -296,11 +305,11 @@ __global__ __launch_bounds__(kWhitBlock) void k_whitted(KParams P, uint32_t* __r
 // The traversal stack (P.bvh_stack entries per thread, 16-bit when the node indices fit) and
 // the top of the tree are in LDS as in k_trace_bvh; the ray ring stays in scratch.  The layout
 // and the policy (WhitBvhLayout, WhitBvh) are in whit_trace.h.
-template <bool TWO, typename SE>
-__global__ __launch_bounds__(kWhitBlock) void k_whitted_bvh(KParams P, uint32_t* __restrict__ work) {
+template <bool TWO, typename SE, bool MOM = false>
+__global__ __launch_bounds__(kWhitBlock) void k_whitted_bvh(KParams P, uint32_t* __restrict__ work, float2* mom) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_whit_bvh[];
     const auto B = whit_bvh_setup<TWO, SE>(P, reinterpret_cast<char*>(lds_whit_bvh), threadIdx.x);
-    whit_pixels(P, B.T, B.st, work, threadIdx.x & 63);
+    whit_pixels<MOM>(P, B.T, B.st, work, threadIdx.x & 63, mom);
 }
 
 // device self-test (xrt_test_whitted_math): the kernel's own geometry functions
@@ -332,19 +341,21 @@ bool use_whitted(const KParams& P) {
 
 // one launch of a Whitted kernel over the shard's pixels: a persistent grid, at most one wave per pixel
 template <typename K>
-static hipError_t whit_launch(K kern, size_t lds, const KParams& P, uint32_t* work, hipStream_t st) {
+static hipError_t whit_launch(K kern, size_t lds, const KParams& P, uint32_t* work, hipStream_t st, float2* mom) {
     uint32_t blocks = 0;
     const hipError_t e = persistent_blocks(kern, kWhitBlock, lds, P.n_slots, &blocks);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWhitBlock), lds, st, P, work);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWhitBlock), lds, st, P, work, mom);
     return hipGetLastError();
 }
 
-hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st) {
+hipError_t launch_whitted(const KParams& P, uint32_t* work, hipStream_t st, float2* mom) {
     if (!use_whitted(P)) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
     return with_scene_kind(P.scene_kind, [&](auto scn) {
-        return whit_launch(k_whitted<decltype(scn)::value>, whit_lds_bytes(P), P, work, st);
+        return with_const<1, 0>(mom != nullptr, [&](auto m) {
+            return whit_launch(k_whitted<decltype(scn)::value, decltype(m)::value != 0>, whit_lds_bytes(P), P, work, st, mom);
+        });
     });
 }
 
@@ -359,11 +370,14 @@ bool use_whitted_bvh(const KParams& P) {
            whit_bvh_lds_bytes(P) <= kPixLds && whit_bvh_lds_bytes(P) <= P.lds_max;
 }
 
-hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st) {
+hipError_t launch_whitted_bvh(const KParams& P, uint32_t* work, hipStream_t st, float2* mom) {
     if (!use_whitted_bvh(P)) return hipErrorInvalidValue;
     if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) return hipErrorInvalidValue;
     return with_whit_bvh(P, [&](auto two, auto se) {
-        return whit_launch(k_whitted_bvh<decltype(two)::value, decltype(se)>, whit_bvh_lds_bytes(P), P, work, st);
+        return with_const<1, 0>(mom != nullptr, [&](auto m) {
+            return whit_launch(k_whitted_bvh<decltype(two)::value, decltype(se), decltype(m)::value != 0>,
+                               whit_bvh_lds_bytes(P), P, work, st, mom);
+        });
     });
 }
 

@@ -118,6 +118,38 @@ class HipRenderer:
         self.stats = st
         return img
 
+    def render_var(self, scene: SceneBundle, width: int, height: int, **kw):
+        """The frame and the variance of each pixel's mean luminance (xrt_render_var): ((H, W, 3),
+        (H, W)) float32.  The frame is render()'s, bit for bit; the variance plane is what
+        denoise_var takes as `variance`.  self.spp must be at least 2.  The path integrators run
+        the wavefront schedule whatever the schedule keywords say; accumulate is refused.  kw:
+        params()'s."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        img = np.zeros((height, width, 3), np.float32)
+        var = np.zeros((height, width), np.float32)
+        st = abi.XrtStats()
+        self._check(self._lib.xrt_render_var(self.ctx, C.byref(p), abi.fptr(img), abi.fptr(var), C.byref(st)),
+                    "xrt_render_var")
+        self.stats = st
+        return img, var
+
+    def render_var_device(self, scene: SceneBundle, width: int, height: int, out_ptr: int, var_ptr: int,
+                          after_stream=None, **kw):
+        """render_var into device buffers (xrt_render_var_device): out_ptr H*W*3 float32, var_ptr
+        H*W float32 (torch tensor .data_ptr()).  after_stream as for render_aov_device.  Returns
+        the stats when both planes are complete."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        st = abi.XrtStats()
+        self._check(self._lib.xrt_render_var_device(self.ctx, C.byref(p), C.c_void_p(out_ptr or None),
+                                                    C.c_void_p(var_ptr or None), C.c_void_p(after_stream or None),
+                                                    C.byref(st)), "xrt_render_var_device")
+        self.stats = st
+        return st
+
     _AOV_SHAPES = {"albedo": (3,), "normal": (3,), "depth": (), "alpha": (), "object": ()}
 
     def render_aov(self, scene: SceneBundle, width: int, height: int,
