@@ -113,15 +113,14 @@ hipError_t launch_refill_merged(const KParams& P, const uint32_t* count, uint32_
 hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
                                 uint32_t blocks, hipStream_t st);
 // merged-trace triangle schedule: eligibility, RNG words one segment may
-// draw, LDS bytes, the per-object kernel-argument records, and the launch (same list /
-// counter contract as launch_step)
+// draw, LDS bytes, and the launch (same list / counter contract as launch_step; SO: the
+// kernel-argument object records, build_step_objs in wavefront.h)
 bool use_step_merged(const KParams& P);
 bool use_step_bvh(const KParams& P);     // two-level scenes: the merged kernel with the wave's BVH walk
 uint32_t step_merged_draws(const KParams& P);
 uint32_t step_merged_spw(const KParams& P, uint64_t live);   // slots per wave for `live` live slots
 uint32_t step_merged_group(const KParams& P, uint32_t spw);  // lanes per slot in group traces (1 = none)
 size_t step_merged_lds_bytes(const KParams& P);
-void build_step_objs(const DObjBox* boxes, const DObjPlane* planes, int n, StepObjs& SO);
 hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,

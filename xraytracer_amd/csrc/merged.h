@@ -285,11 +285,17 @@ __host__ __device__ inline uint32_t merged_wave_off(const KParams& P, const Step
     return merged_plane_off(Lo) + ((8u * (uint32_t)P.n_objs + 15u) & ~15u);
 }
 
+// a ranked ray's id q * 64 + lane (q = 0: extension ray, 1 + l: shadow ray l) takes the low
+// kRayIdBits bits of its record's rd.w; merged_trace puts its object's first triangle above them
+constexpr uint32_t kRayIdBits = 9;
+constexpr uint32_t kRayIds = 1u << kRayIdBits;
+static_assert((1 + kMaxLights) * 64 <= kRayIds && ((uint64_t)kSmallTris << kRayIdBits) < (1ull << 32), "ray records");
+
 template <int NL>
 struct MergedWave {
     static constexpr int R = 1 + NL;   // rays per lane: extension + one shadow ray per light
-    f4 ro[R * 64];                     // the current object's rays, ranked: origin, w = tmax
-    f4 rd[R * 64];                     // direction, w = ray id q * 64 + lane (bits)
+    f4 ro[R * 64];                     // the current class's rays, ranked: origin, w = tmax
+    f4 rd[R * 64];                     // direction, w = first triangle << kRayIdBits | ray id (bits)
     unsigned long long best[64];       // closest hit of the extension ray: (t bits << 32) | tri
     uint32_t occ[64];                  // bit l: shadow ray l is occluded
 };

@@ -86,7 +86,9 @@ __device__ __forceinline__ v3 qsel3(v3 v, int src_lane) {
 // Src/renderer.cpp:44-75); x + 0 spp times is x + 0 once (-0 becomes +0, NaN stays NaN).  So the
 // slot gets the state the path would have ended in (c_shadow and c_rej stay k_seed's 0, rng_g
 // the seeding refill's) and the step kernels, which load it as ST_DONE, drop it from the live
-// list in their first launch.
+// list in their first launch.  The same launch gives a pixel that is not empty its covering
+// triangle, plus 1, in bits ST_COVER_SHIFT.. of the slot's state word (XRT_CAM_COVER): k_step_merged
+// then takes that triangle as the first hit of the pixel's camera rays without a trace.
 __global__ __launch_bounds__(kBlock) void k_camlist(KParams P, uint32_t retire) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= P.n_slots) return;
@@ -164,7 +166,10 @@ __global__ __launch_bounds__(kBlock) void k_camlist(KParams P, uint32_t retire) 
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         px[0] = px[0] + 0.0f, px[1] = px[1] + 0.0f, px[2] = px[2] + 0.0f;
     }
-    if (!P.camlist) return;   // no speculative launches (plan_render): the lists have no reader
+    // the covering triangle has two readers: the lists' (speculative launches, plan_render) and,
+    // where this launch retires, k_step_merged through the slot's state word (XRT_CAM_COVER)
+    const bool cover_out = XRT_CAM_COVER && retire && mask != 0;
+    if (!P.camlist && !cover_out) return;
     // a covering triangle hides the triangles wholly beyond its plane (as seen from o)
     uint64_t keep = mask;
     for (uint64_t cb = cover; cb; cb &= cb - 1ull) {
@@ -187,7 +192,8 @@ __global__ __launch_bounds__(kBlock) void k_camlist(KParams P, uint32_t retire) 
         }
     }
     const int covering = (__builtin_popcountll(keep) == 1 && (keep & cover)) ? __builtin_ctzll(keep) : -1;
-    P.camlist[s] = make_uint4((uint32_t)keep, (uint32_t)(keep >> 32), (uint32_t)covering, 0u);
+    if (cover_out && covering >= 0) P.state[s] |= (uint32_t)(covering + 1) << ST_COVER_SHIFT;
+    if (P.camlist) P.camlist[s] = make_uint4((uint32_t)keep, (uint32_t)(keep >> 32), (uint32_t)covering, 0u);
 }
 
 // ---------------------------------------------------------------- the step kernel ----

@@ -16,12 +16,14 @@
 //    later radiance update of the same path, so every float sum happens in the
 //    reference's order.  A sample that ends with shadow rays in flight is finished after
 //    they resolve (rad_fin), while its successor's camera ray is traced.
-//  * Object-major pair passes: for each object (kernel-argument record, scalar loads) the
-//    wave ballots which of its rays (1 + NL per lane) overlap the object's culling box,
-//    ranks those rays into LDS (mbcnt; origin + tmax, direction + ray id) and tests the
-//    (ray, triangle) pairs 64 per pass,
-//    pair j -> ray rank j / count (magic multiply), triangle first + j % count.  No prefix
-//    scan, no per-lane expansion loop.  Closest hits merge with an LDS atomicMin of
+//  * Class-major pair passes: for each object (kernel-argument record, scalar loads) the
+//    wave ballots which of its rays (1 + NL per lane) overlap the object's culling box and
+//    ranks those rays into LDS (mbcnt; origin + tmax, direction + the object's first triangle
+//    and the ray id), the objects of one triangle count (a class, StepClass) one behind the
+//    other in one stream; then it tests the class's (ray, triangle) pairs 64 per pass,
+//    pair j -> ray rank j / count (magic multiply), triangle first(ray) + j % count.  No prefix
+//    scan, no per-lane expansion loop, no per-pair table: the count is uniform within the
+//    stream.  Closest hits merge with an LDS atomicMin of
 //    (t bits << 32 | triangle): smallest t, ties to the lower triangle index — the
 //    reference's in-order strict `t < best` scan; shadow rays set an occlusion bit.
 //  * The RNG words a segment can use (6 + 2 NL at most) are prefetched into registers by
@@ -57,14 +59,14 @@ __device__ __forceinline__ void merged_trace(const StepObjs& SO, const LScene& L
 #pragma unroll
     for (int l = 0; l < NL; ++l) inv[1 + l] = rcp3c(sd[l]), oi[1 + l] = so[l] * inv[1 + l];
     wave_sync();
-    const int n = SO.n;
-    for (int ob = 0; ob < n; ++ob) {
-        const StepObj B = SO.o[ob];
-        bool need[R];
+    constexpr uint32_t kCap = R * 64;   // ranked rays W.ro / W.rd hold
+    for (int ci = 0; ci < SO.n_cls; ++ci) {
+        const StepClass K = SO.cls[ci];
 #if XRT_TRACE_TLIM
-        // the objects so far: an extension ray skips an object whose box it enters beyond its
+        // the classes so far: an extension ray skips an object whose box it enters beyond its
         // closest hit (every triangle inside lies deeper than the box margin, far above the
-        // float error of either t; ties are still tested), a shadow ray one it is occluded by
+        // float error of either t; ties are still tested), a shadow ray one it is occluded by.
+        // Read once per class: its objects do not cull each other.
         const unsigned long long cur = W.best[lane];
         const float bt = cur == ~0ull ? kINF : __uint_as_float((uint32_t)(cur >> 32));
         const uint32_t done = W.occ[lane];
@@ -72,61 +74,75 @@ __device__ __forceinline__ void merged_trace(const StepObjs& SO, const LScene& L
         const float bt = kINF;
         const uint32_t done = 0u;
 #endif
-        need[0] = ext && !plane_away(o, d, B.axis, B.plane) && obj_overlap(oi[0], inv[0], B, bt);
-#pragma unroll
-        for (int l = 0; l < NL; ++l)
-            need[1 + l] = B.occluder && ((shm & ~done) >> l & 1u) && !plane_away(so[l], sd[l], B.axis, B.plane) &&
-                          obj_overlap(oi[1 + l], inv[1 + l], B, stm[l]);
+        const uint32_t c = K.c, magic = K.magic;
+        // the pair passes over the `tot` rays ranked so far: one (ray, triangle) pair per lane
+        // and step, pair j -> ray j / c and triangle j % c of that ray's object; an
+        // out-of-range lane of the last step tests the last pair again with its result dropped
+        // (no divergent branch; two steps per iteration with both tests before the merges
+        // measured 5% slower on C2)
+        auto passes = [&](uint32_t tot) {
+            wave_sync();
+            const uint32_t pairs = tot * c;
+            for (uint32_t j0 = 0; j0 < pairs; j0 += 64u) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                const bool valid = j < pairs;
+                const uint32_t jj = valid ? j : pairs - 1u;
+                const uint32_t r = c == 1u ? jj : c == 2u ? jj >> 1 : __umulhi(jj, magic);
+                const f4 D = W.rd[r];
+                const f4 A = W.ro[r];
+                const uint32_t e = __float_as_uint(D.w) & (kRayIds - 1u);
+                const uint32_t k = (__float_as_uint(D.w) >> kRayIdBits) + (jj - r * c);
+                const f4 C = L.tri[3 * k + 2];
+                float t;
+                if (ray_tri_nb(xyz(A), xyz(D), xyz(L.tri[3 * k]), xyz(L.tri[3 * k + 1]), xyz(C), t) && valid) {
+                    if (e < 64u)
+                        atomicMin(&W.best[e], ((unsigned long long)__float_as_uint(t) << 32) | (ORIG ? __float_as_uint(C.w) : k));
+                    else if (t < A.w)
+                        atomicOr(&W.occ[e & 63u], 1u << ((e >> 6) - 1u));
+                }
+            }
+            wave_sync();
+        };
         // the rays themselves are ranked into W (not their ids), so a pair reads its ray
-        // with one LDS access instead of an id and then the ray
+        // with one LDS access instead of an id and then the ray; a ray's record carries its
+        // object's first triangle above its id.  An object whose rays would not fit behind
+        // those ranked already waits for their passes and is then ranked from 0.
         uint32_t tot = 0;
+        for (uint32_t ob = K.begin; ob < K.end || tot;) {
+            bool full = ob == K.end;   // wave-uniform: run the passes now (the class's last rays, or no room)
+            if (!full) {
+                const StepObj B = SO.o[ob];
+                bool need[R];
+                need[0] = ext && !plane_away(o, d, B.axis, B.plane) && obj_overlap(oi[0], inv[0], B, bt);
 #pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const uint64_t m = __ballot(need[q]);
-            if (need[q]) {
-                const uint32_t at = tot + lanemask_rank(m);
-                const v3 ro = q == 0 ? o : so[q - 1], rd = q == 0 ? d : sd[q - 1];
-                W.ro[at] = make_float4(ro.x, ro.y, ro.z, q == 0 ? kINF : stm[q - 1]);
-                W.rd[at] = make_float4(rd.x, rd.y, rd.z, __uint_as_float((uint32_t)(q * 64 + lane)));
+                for (int l = 0; l < NL; ++l)
+                    need[1 + l] = B.occluder && ((shm & ~done) >> l & 1u) && !plane_away(so[l], sd[l], B.axis, B.plane) &&
+                                  obj_overlap(oi[1 + l], inv[1 + l], B, stm[l]);
+                uint64_t m[R];
+                uint32_t n_ob = 0;
+#pragma unroll
+                for (int q = 0; q < R; ++q) m[q] = __ballot(need[q]), n_ob += (uint32_t)__popcll(m[q]);
+                full = tot + n_ob > kCap;   // then tot > 0, since n_ob <= kCap: the object is ranked next time round
+                if (!full) {
+                    const uint32_t tag = (uint32_t)B.first << kRayIdBits;
+#pragma unroll
+                    for (int q = 0; q < R; ++q) {
+                        if (need[q]) {
+                            const uint32_t at = tot + lanemask_rank(m[q]);
+                            const v3 ro = q == 0 ? o : so[q - 1], rd = q == 0 ? d : sd[q - 1];
+                            W.ro[at] = make_float4(ro.x, ro.y, ro.z, q == 0 ? kINF : stm[q - 1]);
+                            W.rd[at] = make_float4(rd.x, rd.y, rd.z, __uint_as_float(tag | (uint32_t)(q * 64 + lane)));
+                        }
+                        tot += (uint32_t)__popcll(m[q]);
+                    }
+                    ++ob;
+                }
             }
-            tot += (uint32_t)__popcll(m);
+            if (full) {
+                passes(tot);
+                tot = 0;
+            }
         }
-        if (tot == 0) continue;
-        wave_sync();
-        const uint32_t c = B.count, first = (uint32_t)B.first;
-        const uint32_t pairs = tot * c;
-        const uint32_t magic = B.magic;
-        // one (ray, triangle) pair per lane and step: an out-of-range lane of the last step
-        // tests the last pair again with its result dropped (no divergent branch; two steps
-        // per iteration with both tests before the merges measured 5% slower on C2)
-        struct PairHit {
-            bool hit;
-            uint32_t e, idx;
-            float t, tw;
-        };
-        auto test = [&](uint32_t j) {
-            const bool valid = j < pairs;
-            const uint32_t jj = valid ? j : pairs - 1u;
-            const uint32_t r = (c == 1u) ? jj : __umulhi(jj, magic);
-            const uint32_t k = first + (jj - r * c);
-            const f4 A = W.ro[r];
-            const f4 D = W.rd[r];
-            const f4 C = L.tri[3 * k + 2];
-            PairHit p;
-            p.hit = ray_tri_nb(xyz(A), xyz(D), xyz(L.tri[3 * k]), xyz(L.tri[3 * k + 1]), xyz(C), p.t) && valid;
-            p.e = __float_as_uint(D.w), p.tw = A.w, p.idx = ORIG ? __float_as_uint(C.w) : k;
-            return p;
-        };
-        auto merge = [&](const PairHit& p) {
-            if (p.hit) {
-                if (p.e < 64u)
-                    atomicMin(&W.best[p.e], ((unsigned long long)__float_as_uint(p.t) << 32) | p.idx);
-                else if (p.t < p.tw)
-                    atomicOr(&W.occ[p.e & 63u], 1u << ((p.e >> 6) - 1u));
-            }
-        };
-        for (uint32_t j0 = 0; j0 < pairs; j0 += 64u) merge(test(j0 + (uint32_t)lane));
-        wave_sync();
     }
     best = W.best[lane];
     occ = W.occ[lane];
@@ -500,6 +516,8 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
         // NaN), the exact values resolve() would form from thr_nee and c0 / c1 — so neither
         // thr_nee nor c0 stays live across the trace
         constexpr bool kFold = INTEG == XRT_INTEGRATOR_GI && NL == 1;
+        // the state word's covering triangle is set only where k_camlist retires (plan_render's elide)
+        constexpr bool kCover = XRT_CAM_COVER && INTEG == XRT_INTEGRATOR_GI && !BVH;
         uint32_t c0z = 0;
         float stm[NL + 1];
 #pragma unroll
@@ -589,16 +607,21 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
             const bool act = live && !(st & ST_DONE) && g - rng.c >= (uint32_t)NW;
             if (!__ballot(act || shm)) break;
             const bool ext_now = act && ext;
+            // a camera ray of a pixel that one triangle covers (k_camlist's covering claim, the
+            // triangle + 1 in the state word) hits that triangle first, whatever its jitter: it is
+            // not traced, and the shading below recomputes t, u, v from the triangle as for any hit
+            const bool ext_tr = ext_now && !(kCover && depth == 0 && (st >> ST_COVER_SHIFT));
             unsigned long long best;
             uint32_t occ;
             if constexpr (BVH) {
                 merged_trace<NL, true>(SO, L, W, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
                 deep_pass<NL, uint16_t>(P, top, ntop, stk, W, lane, root, ext_now, o, d, shm, so, sd, stm, best, occ);
             } else if constexpr (!LANE) {
-                merged_trace<NL>(SO, L, W, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
+                merged_trace<NL>(SO, L, W, lane, ext_tr, o, d, shm, so, sd, stm, best, occ);
             } else {
-                group_trace<NL, G>(P.n_objs, L, lplane, lane, ext_now, o, d, shm, so, sd, stm, best, occ);
+                group_trace<NL, G>(P.n_objs, L, lplane, lane, ext_tr, o, d, shm, so, sd, stm, best, occ);
             }
+            if (kCover && ext_now && depth == 0 && (st >> ST_COVER_SHIFT)) best = (st >> ST_COVER_SHIFT) - 1u;
             resolve(occ);
             if (BVH ? pf_pending : vis > 0) rng.take();   // the words prefetched at the end of the previous segment
             if (ext_now) {
@@ -832,22 +855,6 @@ size_t step_merged_lds_bytes(const KParams& P) {
     const size_t w = merged_wave_bytes(P.n_lights);
     if (P.two_level) return bvh_step_layout(P, (uint32_t)w).total;
     return merged_wave_off(P, step_layout(P)) + (kBlock / 64) * w;
-}
-
-void build_step_objs(const DObjBox* boxes, const DObjPlane* planes, int n, StepObjs& SO) {
-    std::memset(&SO, 0, sizeof(SO));
-    SO.n = n;
-    for (int i = 0; i < n; ++i) {
-        StepObj& o = SO.o[i];
-        o.axis = planes[i].axis;
-        o.plane = planes[i].c;
-        for (int q = 0; q < 3; ++q) o.bmin[q] = boxes[i].bmin[q], o.bmax[q] = boxes[i].bmax[q];
-        o.first = boxes[i].first;
-        o.count = (uint32_t)(boxes[i].count_occ & 0x7fffffff);
-        o.occluder = boxes[i].count_occ < 0 ? 1u : 0u;
-        // ceil(2^32 / count): floor(j * magic / 2^32) = j / count for j * count < 2^32
-        o.magic = o.count > 1 ? (uint32_t)(((1ull << 32) + o.count - 1) / o.count) : 0u;
-    }
 }
 
 template <int INTEG, int SPW, int G, bool LANE, bool BVH = false, int WV = 0>

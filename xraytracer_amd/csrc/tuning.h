@@ -25,6 +25,9 @@
 #ifndef XRT_TRACE_TLIM
 #define XRT_TRACE_TLIM 1     // merged_trace: cull objects beyond the ray's closest hit so far / after occlusion (C2 -1.2%)
 #endif
+#ifndef XRT_TRACE_CLASSES
+#define XRT_TRACE_CLASSES 1  // merged_trace: objects of equal triangle count share one ranked stream and its pair passes (C2 -0.9%; 0 is not the former per-object loop but this one with every object a class of its own: C2 +8.6% against that loop, no fallback)
+#endif
 #ifndef XRT_STEP_WAVES
 #define XRT_STEP_WAVES 4     // min waves per SIMD of k_step_merged / k_step (<= 128 VGPRs; 3 or 5: C2 -5% / -9%)
 #endif
@@ -121,6 +124,9 @@
 #endif
 #ifndef XRT_CAM_ELIDE
 #define XRT_CAM_ELIDE 1      // GI, merged schedule: pixels no camera ray can hit are finished by k_camlist (C2: 45.6% of them)
+#endif
+#ifndef XRT_CAM_COVER
+#define XRT_CAM_COVER 1      // ... and a camera ray of a pixel that one triangle covers is not traced by k_step_merged (C2 -2.0% on top of the class streams)
 #endif
 
 // ---- experiment builds

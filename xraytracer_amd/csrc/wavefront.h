@@ -21,6 +21,7 @@
 
 #ifndef __HIPCC__
 struct float4_ { float x, y, z, w; };
+struct uint4;   // plain host code (host/step_classes.cpp) only sees pointers to it
 #endif
 
 namespace xrt {
@@ -64,7 +65,11 @@ enum : uint32_t {
     ST_MEDIUM = 32u,  // VPT delta-tracking loop suspended (resumes after an RNG refill)
     ST_RNGREQ = 64u,  // slot's first twist is pending (k_seed sets it, the seeding k_refill clears it)
     ST_NEEWALK = 128u,// VPT-NEE: the light sample's ratio tracking is suspended (state in KParams::nee)
-    ST_SHADOW_SHIFT = 8u  // bits 8..15: which lights have a shadow ray in flight
+    ST_SHADOW_SHIFT = 8u, // bits 8..15: which lights have a shadow ray in flight
+    // bits 16..22: the triangle that covers the slot's pixel, plus 1, or 0 (k_camlist with `retire`,
+    // XRT_CAM_COVER; read by k_step_merged, which keeps the bits until the slot is ST_DONE; every
+    // other kernel tests single state bits and may drop these)
+    ST_COVER_SHIFT = 16u
 };
 
 enum : int { SEG_TRI = 0, SEG_SPHERE = 1, SEG_BOX = 2 };
@@ -97,14 +102,12 @@ struct DObjBox {
 };
 // Per-object record of the merged-trace triangle kernel (step_tri.hip), passed by value
 // as a kernel argument so the object loop reads it with scalar loads: the culling box
-// (DObjBox's, margin included), the triangle range, whether it occludes (no area light),
-// and magic = ceil(2^32 / count) for the pair -> (ray rank, triangle) split.
+// (DObjBox's, margin included), its first triangle (their count is its class's, StepClass),
+// and whether it occludes (no area light).
 struct StepObj {
     float bmin[3];
     int first;
     float bmax[3];
-    uint32_t count;
-    uint32_t magic;
     uint32_t occluder;
     int axis;      // DObjPlane of the object
     float plane;
@@ -119,10 +122,23 @@ struct DObjPlane {
     float c;
 };
 constexpr int kMergedMaxObjs = 32;
-struct StepObjs {
-    StepObj o[kMergedMaxObjs];
-    int n;
+// A run of StepObjs::o records whose objects have the same triangle count c: the merged trace
+// ranks the rays of all of them into one stream and tests its (ray, triangle) pairs together,
+// pair j -> ranked ray j / c (magic = ceil(2^32 / c), 0 for c = 1), triangle j % c of the
+// ray's object.
+struct StepClass {
+    uint32_t c, magic;
+    uint32_t begin, end;   // o[begin, end)
 };
+struct StepObjs {
+    StepObj o[kMergedMaxObjs];   // class by class (build_step_objs); `first` indexes the scene's triangle array
+    StepClass cls[kMergedMaxObjs];
+    int n, n_cls;
+};
+// The records of n objects (host/step_classes.cpp, plain host code): objects of equal triangle
+// count made contiguous — classes in the order in which their counts first appear, objects
+// inside a class in scene order — or, without XRT_TRACE_CLASSES, every object a class of its own.
+void build_step_objs(const DObjBox* boxes, const DObjPlane* planes, int n, StepObjs& SO);
 constexpr uint32_t kBvhLeaf = 4;      // sphere BVH (C3): primitives per leaf (at most)
 constexpr uint32_t kBvhLeafTri = XRT_BVH_LEAF;   // triangle BVH (C4): triangles per leaf (at most)
 constexpr int kBvhMaxDepth = 48;      // BVH build: depth bound (SAH above max - 24 levels, median below)
