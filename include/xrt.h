@@ -178,6 +178,10 @@ enum {
                                    the scene does not fit LDS (k_whitted_bvh: triangle scenes
                                    with one big mesh or many, XRT_SCHED_WHITTED_BVH); a scene
                                    that fits LDS renders exactly as without the flag           */
+    XRT_FLAG_NO_OVERLAP = 1024u, /* merged schedule: one step launch per round on the context's
+                                   stream, instead of one per partition group on streams of their
+                                   own (the default while whole waves run, XRT_STEP_GROUPS in
+                                   tuning.h); same results                                     */
     XRT_FLAG_ACCUMULATE = 16u  /* Renderer::render's in-place contract (Src/renderer.cpp:75,98):
                                   each owned pixel starts from the value already in the output
                                   buffer (Image::addPixel adds to it in sample order), then
@@ -228,6 +232,12 @@ typedef struct {
     double wall_ms;              /* host wall clock of the render call (upload excluded) */
     double kernel_ms[XRT_K_COUNT];   /* summed HIP-event time per kernel (XRT_FLAG_TIMING) */
     uint64_t launches[XRT_K_COUNT];  /* launches per kernel                                */
+    /* While the merged schedule's step launches run in partition groups, a round is one launch
+     * per group, each on its group's stream: launches[XRT_K_STEP] and layout_launches count every
+     * one of them, `iterations` the rounds.  Their times overlap, so per-launch events would sum to
+     * the groups' number times the wall time: the grouped rounds are timed as one span, from the
+     * fork off the context's stream to the join back into it, and that span is what
+     * kernel_ms[XRT_K_STEP] gets.  kernel_ms / launches stays the time one launch costs the frame. */
     uint64_t samples;            /* pixels * spp rendered by this shard                    */
     uint64_t segments;           /* Scene::intersect calls (extension rays traced)         */
     uint64_t shadow_rays;        /* Scene::occluded calls                                  */

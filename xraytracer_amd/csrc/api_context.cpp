@@ -70,16 +70,18 @@ int xrt_create(int device, xrt_ctx** out) {
     xrt_ctx* c = new xrt_ctx();
     c->device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_poll, 8 * kMaxParts * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_poll, 8 * kMaxStepGroups * kMaxParts * sizeof(uint32_t), hipHostMallocDefault) !=
+            hipSuccess ||
         hipEventCreateWithFlags(&c->wait_ev, hipEventDisableTiming) != hipSuccess) {
         xrt_destroy(c);
         return XRT_ERR_HIP;
     }
-    for (hipEvent_t& e : c->poll_ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            xrt_destroy(c);
-            return XRT_ERR_HIP;
-        }
+    for (auto& slot : c->poll_ev)
+        for (hipEvent_t& e : slot)
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+                xrt_destroy(c);
+                return XRT_ERR_HIP;
+            }
     int lds = 0;
     if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || lds <= 0) {
         xrt_destroy(c);
@@ -96,6 +98,11 @@ void xrt_destroy(xrt_ctx* c) {
     c->subs.clear();
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipStream_t s : c->group_stream)   // joined into c->stream after every render; synchronised all the same
+        if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
+    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    for (hipEvent_t e : c->join_ev)
+        if (e) (void)hipEventDestroy(e);
     DevBuf* all[] = {&c->tri, &c->tri_ng, &c->tri_nrm, &c->sph, &c->sph_obj, &c->box, &c->objs, &c->lights,
                      &c->segs, &c->density, &c->obj_box, &c->obj_plane, &c->bvh_node, &c->bvh_tri, &c->snode, &c->ssph, &c->sbk, &c->sblk, &c->ray_o, &c->ray_d, &c->thr, &c->rad, &c->thr_prev, &c->hit,
                      &c->hit2, &c->hit3, &c->sh_o, &c->sh_d, &c->sh_c, &c->med, &c->med2, &c->nee, &c->state,
@@ -108,8 +115,9 @@ void xrt_destroy(xrt_ctx* c) {
     free_buf(c->dlights), free_buf(c->obj_albedo), free_buf(c->aov), free_buf(c->denoise);
     free_buf(c->mom), free_buf(c->var);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->poll_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (auto& slot : c->poll_ev)
+        for (hipEvent_t e : slot)
+            if (e) (void)hipEventDestroy(e);
     if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
     if (c->h_poll) (void)hipHostFree(c->h_poll);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -230,6 +230,7 @@ struct RenderPlan {
     // ray can hit (spec.hip)
     bool pixel, fused, merged, two_level, step_tri, spec, camlist, elide, whitted, whitted_bvh;
     uint32_t n_part, part_cap;                     // live-list partitions
+    uint32_t groups;                               // partition groups of the merged schedule's full-wave launches (1: none)
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
     uint64_t cap_iters;                            // loop iterations at most
@@ -237,6 +238,8 @@ struct RenderPlan {
     // builds of k_shade / k_whitted / k_whitted_bvh; null for a plain render
     float2* mom;
 };
+
+static_assert(XRT_STEP_GROUPS >= 1 && XRT_STEP_GROUPS <= (int)kMaxStepGroups, "XRT_STEP_GROUPS: 1..3");
 
 RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom) {
     RenderPlan R{};
@@ -284,6 +287,11 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom
     R.n_part = (uint32_t)std::min<size_t>(cap, std::max<size_t>(1, n / per));
     if (R.n_part >= 8) R.n_part &= ~7u;
     R.part_cap = (uint32_t)((n + R.n_part - 1) / R.n_part);
+    // the merged schedule's full-wave launches in partition groups (step_groups.h): one-level
+    // scenes; the two-level kernel's launches are not measured in groups and stay whole
+    R.groups = R.merged && !R.two_level && !R.pixel && !R.whitted && !(p->flags & XRT_FLAG_NO_OVERLAP)
+                   ? step_groups_for(R.n_part, XRT_STEP_GROUPS)
+                   : 1u;
     // segments per slot per step launch: kMergedVisits / kStepVisits unless the caller sets
     // visits_per_launch (results do not depend on it)
     const uint32_t draws = step_merged_draws(P);
@@ -322,7 +330,11 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom
 // the copy.  Polls are retired in order: without blocking once their event has fired, by
 // waiting once the host is `ahead` iterations past one.  Retired polls give `done` (no live
 // slot left) and the live counts the merged schedule chooses its layout and grid by (upper
-// bounds: paths only finish).
+// bounds: paths only finish).  An iteration launched in G partition groups (run_fused) is polled
+// without a barrier between the groups: each group copies the counters on its own stream, in
+// order behind its launch, into pinned slots of its own, of which the host reads that group's
+// partitions only, and the poll is retired when every group's event has fired.  The live counts
+// are taken over all groups, so they keep their whole-GPU meaning.
 struct LivePoll {
     xrt_ctx* c;
     uint32_t n_part;
@@ -331,27 +343,38 @@ struct LivePoll {
     uint64_t live_hint;       // live slots at the last retired poll
     uint32_t live_part_max;   // ... in the fullest partition
     bool done = false;
-    struct Pending { uint64_t it; int slot; };
+    struct Pending { uint64_t it; int slot; uint32_t groups; };
     std::vector<Pending> pending;
     int issued = 0;
 
-    // after iteration `it`, whose launches left the live counts in `live` (device)
-    int after(uint64_t it, const uint32_t* live) {
+    // after iteration `it`, whose launches left the live counts in `live` (device); groups > 1: one
+    // launch per partition group, on c->group_stream
+    int after(uint64_t it, const uint32_t* live, uint32_t groups = 1) {
         if (it % every == every - 1) {
             const int ps = issued++ % 8;
-            HIPCHK(c, hipMemcpyAsync(c->h_poll + ps * kMaxParts, live, n_part * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipEventRecord(c->poll_ev[ps], c->stream));
-            pending.push_back({it, ps});
+            for (uint32_t g = 0; g < groups; ++g) {
+                hipStream_t st = groups > 1 ? c->group_stream[g] : c->stream;
+                HIPCHK(c, hipMemcpyAsync(c->h_poll + (ps * kMaxStepGroups + g) * kMaxParts, live, n_part * 4,
+                                         hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipEventRecord(c->poll_ev[ps][g], st));
+            }
+            pending.push_back({it, ps, groups});
         }
         while (!pending.empty()) {
             const Pending q = pending.front();
             const bool must_wait = it - q.it >= ahead;
-            if (!must_wait && hipEventQuery(c->poll_ev[q.slot]) != hipSuccess) break;
-            HIPCHK(c, hipEventSynchronize(c->poll_ev[q.slot]));
-            const uint32_t* h = c->h_poll + q.slot * kMaxParts;
+            bool fired = true;
+            for (uint32_t g = 0; g < q.groups && fired && !must_wait; ++g)
+                fired = hipEventQuery(c->poll_ev[q.slot][g]) == hipSuccess;
+            if (!fired) break;
+            for (uint32_t g = 0; g < q.groups; ++g) HIPCHK(c, hipEventSynchronize(c->poll_ev[q.slot][g]));
+            const uint32_t* h0 = c->h_poll + (size_t)q.slot * kMaxStepGroups * kMaxParts;
             uint64_t alive = 0;
             uint32_t pmax = 0;
-            for (uint32_t k = 0; k < n_part; ++k) alive += h[k], pmax = std::max(pmax, h[k]);
+            for (uint32_t k = 0; k < n_part; ++k) {
+                const uint32_t v = h0[step_group_of(q.groups, k) * kMaxParts + k];
+                alive += v, pmax = std::max(pmax, v);
+            }
             if (alive == 0) done = true;
             if (alive < live_hint) {
                 live_hint = alive;
@@ -399,18 +422,83 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
 // from the live count of the last retired poll, so a frame's tail, where few slots remain,
 // runs with more lanes per slot, and sizes the grid by the fullest partition's
 // live count instead of its capacity.  Results never depend on the layout.
+//
+// While the merged schedule runs whole waves (64 slots each) and the plan has partition groups
+// (RenderPlan::groups, step_groups.h), an iteration is one launch per group, each on the group's
+// own stream, so one group's last waves do not hold back the next round of the others.  All of
+// them are launches of the same iteration: the list ping-pong and the counter rotation stay
+// common, each launch reading, appending to and clearing its own group's partitions.  The group
+// streams leave c->stream by an event before the first such iteration and join it again, by
+// events, when the layout leaves 64 slots per wave, when the loop ends and when a call fails;
+// from the join on the loop runs as it does without groups.  Nothing waits on the device.
+class StepGroupStreams {
+  public:
+    StepGroupStreams(xrt_ctx* c, LaunchTimer& T, uint32_t groups) : c_(c), T_(T), groups_(groups) {}
+    ~StepGroupStreams() { (void)join(); }   // an error path: bring the streams back all the same
+    bool forked() const { return forked_; }
+    // the group streams (made with the context's first grouped render) wait for c->stream's work so far
+    int fork() {
+        if (forked_) return XRT_OK;
+        for (uint32_t g = 0; g < groups_; ++g) {
+            if (!c_->group_stream[g]) HIPCHK(c_, hipStreamCreateWithFlags(&c_->group_stream[g], hipStreamNonBlocking));
+            if (!c_->join_ev[g]) HIPCHK(c_, hipEventCreateWithFlags(&c_->join_ev[g], hipEventDisableTiming));
+        }
+        if (!c_->fork_ev) HIPCHK(c_, hipEventCreateWithFlags(&c_->fork_ev, hipEventDisableTiming));
+        T_.span_begin(XRT_K_STEP);
+        HIPCHK(c_, hipEventRecord(c_->fork_ev, c_->stream));
+        forked_ = true;   // from here on a join is owed, whatever fails
+        for (uint32_t g = 0; g < groups_; ++g) HIPCHK(c_, hipStreamWaitEvent(c_->group_stream[g], c_->fork_ev, 0));
+        return XRT_OK;
+    }
+    // c->stream waits for every group stream's work so far
+    int join() {
+        if (!forked_) return XRT_OK;
+        forked_ = false;
+        hipError_t first = hipSuccess;
+        for (uint32_t g = 0; g < groups_; ++g) {
+            hipError_t e = hipEventRecord(c_->join_ev[g], c_->group_stream[g]);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c_->stream, c_->join_ev[g], 0);
+            if (first == hipSuccess) first = e;
+        }
+        T_.span_end();
+        return first == hipSuccess ? XRT_OK : hip_err(c_, first, "joining the step group streams");
+    }
+
+  private:
+    xrt_ctx* c_;
+    LaunchTimer& T_;
+    uint32_t groups_;
+    bool forked_ = false;
+};
+
 int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, LivePoll& poll,
               uint64_t& it) {
     const KParams* dP = as<KParams>(c->kparams);
     const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // k_step, k_step_tri: one entry per thread
     // built before the first launch that reads them (seed_paths has when it elides), timed with the seeding
     bool camlist_pending = R.camlist && !R.elide;
+    StepGroupStreams GS(c, T, R.groups);
     for (it = 0; it < R.cap_iters && !poll.done; ++it) {
         const uint32_t *list = L.list[it & 1], *ci = L.counts(it % 3);
         uint32_t *out = L.list[~it & 1], *co = L.counts((it + 1) % 3), *cz = L.counts((it + 2) % 3);
-        T.step_live.push_back(poll.live_hint);
         const uint32_t spw = R.merged ? step_merged_spw(P, poll.live_hint) : 0;
-        if (R.merged) T.S.layout_launches[spw == 64 ? 0 : spw == 32 ? 1 : spw == 16 ? 2 : spw == 8 ? 3 : 4]++;
+        const uint32_t groups = spw == 64 ? R.groups : 1u;
+        // one entry per timed step entry: a span of grouped rounds is one (the live hint it began with)
+        if (groups == 1 || !GS.forked()) T.step_live.push_back(poll.live_hint);
+        if (R.merged) T.S.layout_launches[spw == 64 ? 0 : spw == 32 ? 1 : spw == 16 ? 2 : spw == 8 ? 3 : 4] += groups;
+        int rc;
+        if (groups > 1) {
+            if ((rc = GS.fork())) return rc;
+            for (uint32_t g = 0; g < groups; ++g) {
+                const hipError_t e = launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
+                                                        poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g]);
+                if (e != hipSuccess) return hip_err(c, e, "k_step");
+            }
+            T.S.launches[XRT_K_STEP] += groups;
+            if ((rc = poll.after(it, co, groups))) return rc;
+            continue;
+        }
+        if ((rc = GS.join())) return rc;
         // speculative starts in the group layouts (4 lanes per slot; 16 in the tail; 8 when forced)
         const bool spec_now = R.spec && P.camlist && (spw == 16 || spw == 8 || (XRT_SPEC_TAIL && spw == 4)) &&
                               step_merged_group(P, spw) * spw == 64;
@@ -424,15 +512,14 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
                 return launch_step_spec(P, dP, list, ci, out, co, cz, R.spec_visits, poll.live_part_max, spw, c->stream);
             if (R.merged)
                 return launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
-                                          poll.live_hint, poll.live_part_max, c->stream);
+                                          poll.live_hint, poll.live_part_max, 1, 0, c->stream);
             return launch_step(P, dP, list, ci, out, co, cz, L.req(1), R.step_visits, blocks, poll.live_hint, R.step_tri,
                                c->stream);
         });
         if (e != hipSuccess) return hip_err(c, e, "k_step");
-        const int rc = poll.after(it, co);
-        if (rc) return rc;
+        if ((rc = poll.after(it, co))) return rc;
     }
-    return XRT_OK;
+    return GS.join();
 }
 
 // The wavefront loop: k_shade reads list[i & 1] and appends the surviving slots to the other
@@ -556,6 +643,9 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
         return e != hipSuccess || !R.mom ? e : launch_finish_var(P, R.mom, d_var, c->stream);
     }));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+#if XRT_PHASE_CLOCK
+    HIPCHK(c, wave_clock_dump(exp_env("XRT_WAVE_CLOCK_OUT"), c->stream));
+#endif
     if (!R.pixel && !poll.done) {
         // the iteration cap was reached without observing an empty list: verify
         uint32_t left[kMaxParts] = {0};

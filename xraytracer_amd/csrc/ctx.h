@@ -46,10 +46,15 @@ struct xrt_ctx {
     // xrt_render_var: per slot the {s1, s2} luminance moments (float2), and the context's own
     // variance plane (host output, sub-contexts of a multi render)
     xrt::DevBuf mom, var;
-    uint32_t* h_poll = nullptr;  // pinned: LivePoll's 8 slots of kMaxParts counts
+    uint32_t* h_poll = nullptr;  // pinned: LivePoll's 8 slots of kMaxParts counts for each of kMaxStepGroups groups
     std::vector<hipEvent_t> events;   // LaunchTimer's pairs
-    hipEvent_t poll_ev[8] = {};  // LivePoll's events (created once)
+    hipEvent_t poll_ev[8][xrt::kMaxStepGroups] = {};  // LivePoll's events (created once), slot by group
     hipEvent_t wait_ev = nullptr;   // xrt_render_device_after: the caller stream's position
+    // the merged schedule's partition groups (step_groups.h): a stream per group, created with
+    // the first render that runs grouped (group_streams), and the events by which they leave
+    // the context's stream and come back to it
+    hipStream_t group_stream[xrt::kMaxStepGroups] = {};
+    hipEvent_t fork_ev = nullptr, join_ev[xrt::kMaxStepGroups] = {};
     // multi-GPU context (xrt_create_multi): one sub-context per device, each rendering an
     // interleaved row shard; the frame is assembled in subs[0]'s framebuffer
     std::vector<xrt_ctx*> subs;
@@ -131,6 +136,27 @@ struct LaunchTimer {
         if (timed) (void)hipEventRecord(c->events[e + 1], c->stream);
         S.launches[kid]++;
         return err;
+    }
+    // Launches that overlap on other streams, timed as one span with one pair: span_begin on
+    // c->stream before they fork off it, span_end once they have joined it again.  The caller
+    // counts the launches.
+    bool span_open = false;
+    size_t span_stop = 0;   // the open span's second event
+    void span_begin(int kid) {
+        const size_t e = 2 * kids.size();
+        bool timed = timing;
+        while (timed && c->events.size() < e + 2) {
+            hipEvent_t ev;
+            if ((timed = hipEventCreate(&ev) == hipSuccess)) c->events.push_back(ev);
+        }
+        if (!timed) return;
+        kids.push_back(kid);
+        (void)hipEventRecord(c->events[e], c->stream);
+        span_open = true, span_stop = e + 1;
+    }
+    void span_end() {
+        if (span_open) (void)hipEventRecord(c->events[span_stop], c->stream);
+        span_open = false;
     }
     void read_out();
 };

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "step_groups.h"
 #include "wavefront.h"
 
 namespace xrt {
@@ -121,10 +122,18 @@ uint32_t step_merged_draws(const KParams& P);
 uint32_t step_merged_spw(const KParams& P, uint64_t live);   // slots per wave for `live` live slots
 uint32_t step_merged_group(const KParams& P, uint32_t spw);  // lanes per slot in group traces (1 = none)
 size_t step_merged_lds_bytes(const KParams& P);
+// groups, group: the launch serves the partitions of group `group` of `groups` only (step_groups.h:
+// their lists, their counters in out_count and zero); 1, 0: every partition.  live and
+// live_part_max are the whole shard's either way
 hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
-                              hipStream_t st);
+                              uint32_t groups, uint32_t group, hipStream_t st);
+#if XRT_PHASE_CLOCK
+// experiment builds: the merged kernels' per-wave entry / exit clocks of the work queued on st so far,
+// written to `path` (null: dropped) and cleared; tools/wave_timeline.py reads the file
+hipError_t wave_clock_dump(const char* path, hipStream_t st);
+#endif
 
 // ----------------------------------------------------------------------- spec.hip ----
 // speculative sample starts for the merged schedule's group layouts: eligibility,

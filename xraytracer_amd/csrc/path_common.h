@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
+#include "step_groups.h"
 #include "wavefront.h"
 #include "xrt.h"
 
@@ -313,6 +314,27 @@ __device__ __forceinline__ PartIter part_iter(const KParams& P, const uint32_t* 
 __device__ __forceinline__ void zero_parts(const KParams& P, uint32_t* c) {
     if (blockIdx.x == 0)
         for (uint32_t i = threadIdx.x; i < P.n_part; i += kBlock) c[i] = 0;
+}
+// The same two for a launch that serves one partition group (step_groups.h; grp: step_group_arg):
+// the grid is a multiple of the group's partition count, block b serves the group's partition
+// b % that count, whose octet keeps b % 8, and only the group's counters are cleared — another
+// group's launch of the round before may still be appending to its own.
+__device__ __forceinline__ PartIter part_iter(const uint32_t* count, uint32_t per_block, uint32_t grp) {
+    const uint32_t np = grp >> 8;
+    PartIter it;
+    // block-uniform values, said to be so: left to itself the compiler keeps some of them in vector
+    // registers across k_step_merged's loop (GI, one light, 64 slots: 8 spilled VGPRs for 2)
+    auto uni = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+    it.p = uni(step_group_part((grp >> 4) & 15u, grp & 15u, blockIdx.x % np));
+    const uint32_t chunk = blockIdx.x / np, nchunks = gridDim.x / np;
+    it.first = uni(chunk * per_block);
+    it.stride = uni(nchunks * per_block);
+    it.n = uni(count[it.p]);
+    return it;
+}
+__device__ __forceinline__ void zero_parts(uint32_t* c, uint32_t grp) {
+    if (blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < (grp >> 8); i += kBlock) c[step_group_part((grp >> 4) & 15u, grp & 15u, i)] = 0;
 }
 
 

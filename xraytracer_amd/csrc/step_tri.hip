@@ -31,6 +31,9 @@
 //
 // GIIntegrator with maxDepth 0 and scenes with more than kMergedMaxObjs objects keep using
 // k_step_tri.
+#include <cstdio>
+#include <vector>
+
 #include "bvh.h"
 #include "launch.h"
 #include "merged.h"
@@ -413,14 +416,72 @@ hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const ui
 // the hit triangle's shading data from global memory.  Same path
 // code otherwise.
 
-// WV (two-level scenes): a register budget for WV waves per SIMD instead of XRT_BVH_WAVES, for
-// launches with too few live slots to fill more (fewer spills)
-template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, int WV = 0>
-__global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_WAVES)) void k_step_merged(
-    const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ list,
+// Experiment builds (XRT_PHASE_CLOCK, tools/wave_timeline.py): lane 0 of every wave of the merged
+// kernels records the constant-rate wall clock and the shader clock at entry and at exit, one
+// record per wave in launch order of arrival; render_impl writes the records of a render to the
+// file XRT_WAVE_CLOCK_OUT names (wave_clock_dump).  tag: the launch's group argument, ~0 ungrouped.
+#if XRT_PHASE_CLOCK
+constexpr uint32_t kWaveClockCap = 1u << 20;
+struct WaveClockRec {
+    uint32_t tag, block;
+    unsigned long long wall0, shader0, wall1, shader1;
+};
+__device__ WaveClockRec g_wave_clock[kWaveClockCap];
+__device__ unsigned int g_wave_clock_n;
+struct WaveClock {
+    uint32_t idx = kWaveClockCap;
+    __device__ explicit WaveClock(uint32_t tag) {
+        if ((threadIdx.x & 63u) == 0u) {
+            idx = atomicAdd(&g_wave_clock_n, 1u);
+            if (idx < kWaveClockCap) {
+                g_wave_clock[idx].tag = tag, g_wave_clock[idx].block = blockIdx.x;
+                g_wave_clock[idx].wall0 = wall_clock64(), g_wave_clock[idx].shader0 = clock64();
+            }
+        }
+    }
+    __device__ void end() {
+        if (idx < kWaveClockCap) g_wave_clock[idx].wall1 = wall_clock64(), g_wave_clock[idx].shader1 = clock64();
+    }
+};
+hipError_t wave_clock_dump(const char* path, hipStream_t st) {
+    unsigned int n = 0, zero = 0;
+    int khz = 0, dev = 0;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_wave_clock_n), sizeof(n));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_wave_clock_n), &zero, sizeof(zero));
+    if (e == hipSuccess) e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
+    if (e != hipSuccess || !path) return e;
+    n = std::min(n, kWaveClockCap);
+    std::vector<WaveClockRec> rec(n);
+    if (n) e = hipMemcpyFromSymbol(rec.data(), HIP_SYMBOL(g_wave_clock), (size_t)n * sizeof(WaveClockRec));
+    if (e != hipSuccess) return e;
+    if (FILE* f = std::fopen(path, "wb")) {   // header: record count, wall clock kHz; then the records
+        const uint32_t head[2] = {n, (uint32_t)khz};
+        std::fwrite(head, sizeof(head), 1, f);
+        std::fwrite(rec.data(), sizeof(WaveClockRec), n, f);
+        std::fclose(f);
+    }
+    return hipSuccess;
+}
+#else
+struct WaveClock {
+    __device__ explicit WaveClock(uint32_t) {}
+    __device__ void end() {}
+};
+#endif
+
+// GROUPED: the launch serves one partition group (step_groups.h; grp: step_group_arg) — the body of
+// k_step_merged_group.  Without it the body of k_step_merged, every partition, grp unused.
+template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, bool GROUPED>
+__device__ __forceinline__ void step_merged_body(
+    const KParams* __restrict__ Pp, const StepObjs SO,   // by value as the kernels take it (by reference: 4 spilled VGPRs in the group kernel for 2)
+    const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
-    uint32_t* req_count, uint32_t visits) {
+    uint32_t* req_count, uint32_t visits, uint32_t grp) {
     constexpr int NW = 6 + 2 * NL;   // most words one segment draws (see the header)
+    static_assert(!GROUPED || (SPW == 64 && G == 1 && !LANE && !BVH), "groups: whole waves of one-level scenes");
+    WaveClock wclk(GROUPED ? grp : ~0u);   // experiment builds (XRT_PHASE_CLOCK): the wave's entry and exit clocks
     static_assert(!BVH || (G == 1 && !LANE), "two-level scenes trace by pair passes");
     const KParams& P = *Pp;
     extern __shared__ __attribute__((aligned(16))) f4 lds_m[];
@@ -493,8 +554,11 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
         }
     };
     __syncthreads();
-    zero_parts(P, zero_count);
-    const PartIter it = part_iter(P, count, (kBlock / 64) * SPW);
+    // the launch's partition group (step_groups.h): its partitions' lists and counters only.
+    // req_count is not touched here (only the seeding refill reads a request list)
+    if constexpr (GROUPED) zero_parts(zero_count, grp);
+    else zero_parts(P, zero_count);
+    const PartIter it = GROUPED ? part_iter(count, (kBlock / 64) * SPW, grp) : part_iter(P, count, (kBlock / 64) * SPW);
     const uint32_t spp = P.spp, max_depth = P.max_depth, width = P.width;
     for (uint32_t base = it.first; base < it.n; base += it.stride) {
         const uint32_t i = base + (uint32_t)(tid >> 6) * SPW + (uint32_t)lane / G;
@@ -771,6 +835,28 @@ __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_W
         wave_append(live && lead && !(st & ST_DONE), s, out + it.p * P.part_cap, out_count + it.p, lane);
         wave_refill(P, want_req, s, g, lane, reinterpret_cast<uint32_t*>(&W));
     }
+    wclk.end();
+}
+
+// WV (two-level scenes): a register budget for WV waves per SIMD instead of XRT_BVH_WAVES, for
+// launches with too few live slots to fill more (fewer spills)
+template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, int WV = 0>
+__global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_WAVES)) void k_step_merged(
+    const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ list,
+    const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
+    uint32_t* req_count, uint32_t visits) {
+    step_merged_body<INTEG, NL, SPW, G, LANE, BVH, false>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, 0u);
+}
+
+// The same kernel for one partition group of a round (whole waves of a one-level scene): the group
+// as one trailing argument.  A kernel of its own, so that a launch of every partition stays the
+// kernel it was, argument list included.
+template <int INTEG, int NL>
+__global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_merged_group(
+    const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ list,
+    const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
+    uint32_t* req_count, uint32_t visits, uint32_t grp) {
+    step_merged_body<INTEG, NL, 64, 1, false, false, true>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, grp);
 }
 
 // CLEAR: also clear the slot's ST_RNGREQ (the wavefront / k_step schedules, whose kernels
@@ -860,14 +946,25 @@ size_t step_merged_lds_bytes(const KParams& P) {
 template <int INTEG, int SPW, int G, bool LANE, bool BVH = false, int WV = 0>
 static void launch_merged_i(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                             const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
-                            uint32_t* req_count, uint32_t visits, uint32_t part_live, size_t lds, hipStream_t st) {
+                            uint32_t* req_count, uint32_t visits, uint32_t part_live, size_t lds, uint32_t grp,
+                            hipStream_t st) {
     // one block per per_block live entries of the fullest partition (part_iter strides over
-    // any remainder, so an upper bound on the live count is all the grid needs)
+    // any remainder, so an upper bound on the live count is all the grid needs), for each of
+    // the partitions the launch's group holds
     const uint32_t per_block = (kBlock / 64) * SPW;
-    const uint32_t blocks = P.n_part * ((std::min(part_live, P.part_cap) + per_block - 1) / per_block);
+    const uint32_t blocks = (grp >> 8) * ((std::min(part_live, P.part_cap) + per_block - 1) / per_block);
     auto go = [&](auto nl) {
-        hipLaunchKernelGGL((k_step_merged<INTEG, decltype(nl)::value, SPW, G, LANE, BVH, WV>), dim3(blocks), dim3(kBlock), lds,
-                           st, dP, SO, list, count, out, out_count, zero, req_count, visits);
+        constexpr int NL = decltype(nl)::value;
+        // one of several groups (launch_step_merged has checked that the layout is the whole-wave one)
+        if constexpr (SPW == 64 && G == 1 && !LANE && !BVH) {
+            if (((grp >> 4) & 15u) > 1u) {
+                hipLaunchKernelGGL((k_step_merged_group<INTEG, NL>), dim3(blocks), dim3(kBlock), lds, st, dP, SO, list, count,
+                                   out, out_count, zero, req_count, visits, grp);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_step_merged<INTEG, NL, SPW, G, LANE, BVH, WV>), dim3(blocks), dim3(kBlock), lds, st, dP, SO,
+                           list, count, out, out_count, zero, req_count, visits);
     };
     if constexpr (BVH) with_const<1, 2>(P.n_lights, go);   // use_step_bvh: 1 or 2 lights
     else with_const<0, 1, 2, 3, 4>(P.n_lights, go);
@@ -905,13 +1002,13 @@ template <int INTEG>
 static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t part_live, size_t lds,
-                              hipStream_t st) {
+                              uint32_t grp, hipStream_t st) {
     const bool group = P.n_tris <= 64 && !(P.rflags & XRT_FLAG_NO_GROUP);   // group trace: 64-bit triangle masks
     const bool lane64 = group && exp_env("XRT_LANE_TRACE");   // experiment: per-lane traces, full waves
     if (P.two_level) {   // use_step_bvh (never group traces: n_tris > 64)
 #define XRT_BVH_CASE(SPWV) \
     launch_merged_i<INTEG, SPWV, 1, false, true>(P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, \
-                                                 part_live, lds, st)
+                                                 part_live, lds, grp, st)
         switch (step_merged_spw(P, live)) {
             case 64: XRT_BVH_CASE(64); break;
             case 32: XRT_BVH_CASE(32); break;
@@ -920,7 +1017,7 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
                 // XRT_BVH_LOW_WAVES build: more registers per wave, fewer spills
                 if (live < XRT_BVH_LOW_LIVE)
                     launch_merged_i<INTEG, 16, 1, false, true, XRT_BVH_LOW_WAVES>(
-                        P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, part_live, lds, st);
+                        P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, part_live, lds, grp, st);
                 else
                     XRT_BVH_CASE(16);
                 break;
@@ -929,7 +1026,7 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
         return;
     }
 #define XRT_MERGED_CASE(SPWV, GV, LV) \
-    launch_merged_i<INTEG, SPWV, GV, LV>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, part_live, lds, st)
+    launch_merged_i<INTEG, SPWV, GV, LV>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, part_live, lds, grp, st)
     switch (step_merged_spw(P, live)) {
         case 64: if (lane64) XRT_MERGED_CASE(64, 1, true); else XRT_MERGED_CASE(64, 1, false); break;
         case 32: if (group) XRT_MERGED_CASE(32, 2, true); else XRT_MERGED_CASE(32, 1, false); break;
@@ -943,11 +1040,15 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
 hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
-                              hipStream_t st) {
+                              uint32_t groups, uint32_t group, hipStream_t st) {
+    if (group >= groups || !step_groups_eligible(P.n_part, groups)) return hipErrorInvalidValue;
+    // groups exist for whole waves of one-level scenes traced by pair passes (k_step_merged_group)
+    if (groups > 1 && (P.two_level || step_merged_spw(P, live) != 64 || exp_env("XRT_LANE_TRACE"))) return hipErrorInvalidValue;
+    const uint32_t grp = step_group_arg(P.n_part, groups, group);
     const size_t lds = step_merged_lds_bytes(P);
     with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {   // use_step_merged / _bvh
         launch_merged_spw<decltype(integ)::value>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, live,
-                                                  live_part_max, lds, st);
+                                                  live_part_max, lds, grp, st);
     });
     return hipGetLastError();
 }

@@ -31,6 +31,9 @@
 #ifndef XRT_STEP_WAVES
 #define XRT_STEP_WAVES 4     // min waves per SIMD of k_step_merged / k_step (<= 128 VGPRs; 3 or 5: C2 -5% / -9%)
 #endif
+#ifndef XRT_STEP_GROUPS
+#define XRT_STEP_GROUPS 2    // k_step_merged's full-wave launches of one-level scenes in this many partition groups, each on a stream of its own (1..3; step_groups.h; C2 66.4 -> 51.5 ms; 3: 83.7 ms; 1: one launch per round, the former sequence, 66.2 ms)
+#endif
 #ifndef XRT_KSTEP_LDS_REFILL
 #define XRT_KSTEP_LDS_REFILL 2   // k_step in-line refill staged through LDS: 1 always, 2 except sphere-BVH scenes, 0 never
 #endif
@@ -131,7 +134,7 @@
 
 // ---- experiment builds
 #ifndef XRT_PHASE_CLOCK
-#define XRT_PHASE_CLOCK 0    // k_step_spec: per-phase shader-clock cycles per wave into stats words 40..47
+#define XRT_PHASE_CLOCK 0    // k_step_spec: per-phase shader-clock cycles per wave into stats words 40..47; the merged kernels: every wave's entry and exit clocks (tools/wave_timeline.py)
 #endif
 
 // ---- volumetric k_step (C5)

@@ -70,7 +70,7 @@ class HipRenderer:
 
     def params(self, scene, width, height, shard_index=0, shard_count=1, timing=False, integrator=None,
                max_depth=None, schedule="auto", slots_per_wave=0, visits_per_launch=0, group=True,
-               accumulate=False, deep="auto", spec=True, whitted_bvh=False):
+               accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True):
         """schedule: "auto" (fused k_step when the scene fits in LDS — for small triangle
         scenes with merged shadow + extension traces, for Direct / Normal pixel-parallel
         sample chains (k_pixel) — else the multi-pass wavefront), "step" (the per-slot fused
@@ -85,7 +85,9 @@ class HipRenderer:
         schedule's 16-slot launches (GI with one light; spec=False sets XRT_FLAG_NO_SPEC); results
         never depend on it.  whitted_bvh: WhittedIntegrator may render a triangle scene that does
         not fit LDS through its triangle BVH (XRT_FLAG_WHITTED_BVH, XRT_SCHED_WHITTED_BVH) instead
-        of refusing it; a scene that fits LDS renders as without it."""
+        of refusing it; a scene that fits LDS renders as without it.  overlap: the merged schedule's
+        full-wave step launches run in partition groups on streams of their own (overlap=False sets
+        XRT_FLAG_NO_OVERLAP: one launch per round); results never depend on it."""
         if schedule not in ("auto", "step", "wavefront", "step_tri"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if deep not in ("auto", "single", "quad"):
@@ -99,7 +101,7 @@ class HipRenderer:
                    (abi.XRT_FLAG_NO_MERGED if schedule == "step_tri" else 0) | (0 if group else abi.XRT_FLAG_NO_GROUP) |
                    (abi.XRT_FLAG_NO_PIXEL if schedule in ("step", "step_tri") else 0) |
                    (abi.XRT_FLAG_ACCUMULATE if accumulate else 0) | (0 if spec else abi.XRT_FLAG_NO_SPEC) |
-                   (abi.XRT_FLAG_WHITTED_BVH if whitted_bvh else 0) |
+                   (abi.XRT_FLAG_WHITTED_BVH if whitted_bvh else 0) | (0 if overlap else abi.XRT_FLAG_NO_OVERLAP) |
                    {"auto": 0, "single": abi.XRT_FLAG_DEEP_SINGLE, "quad": abi.XRT_FLAG_DEEP_QUAD}[deep])
         p.slots_per_wave, p.visits_per_launch = slots_per_wave, visits_per_launch
         return p
