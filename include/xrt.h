@@ -182,6 +182,14 @@ enum {
                                    stream, instead of one per partition group on streams of their
                                    own (the default while whole waves run, XRT_STEP_GROUPS in
                                    tuning.h); same results                                     */
+    XRT_FLAG_INTERLEAVE = 2048u, /* merged schedule: slot s renders pixel s * A mod n of the shard's
+                                   n pixels, so every wave of 64 slots samples the whole shard
+                                   (csrc/slot_map.h).  By default a merged render of a large shard
+                                   does (XRT_SLOT_INTERLEAVE in tuning.h); this flag makes a merged
+                                   render of any size do it.  No effect on the other schedules;
+                                   same results                                                 */
+    XRT_FLAG_NO_INTERLEAVE = 4096u, /* ... and this one keeps every render on the row-major map
+                                   (slot s = pixel s); it wins over XRT_FLAG_INTERLEAVE          */
     XRT_FLAG_ACCUMULATE = 16u  /* Renderer::render's in-place contract (Src/renderer.cpp:75,98):
                                   each owned pixel starts from the value already in the output
                                   buffer (Image::addPixel adds to it in sample order), then
@@ -632,6 +640,13 @@ int xrt_test_whitted_math(xrt_ctx* ctx, const float* in, uint32_t n, float* out)
  * the bits and the covering triangle count triangles in object order.  XRT_ERR_STATE unless the
  * scene is a triangle scene of 1 to 64 triangles.  Nothing a later render reads is left changed. */
 int xrt_test_camlist(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
+/* The slot -> pixel map (csrc/slot_map.h) a render of p would use, read back from the device
+ * function the kernels call: out[s] = col + width * row of slot s, for the n slots of p's row
+ * shard.  The row-major map gives out[s] = s for an unsharded image.  Needs an uploaded scene and
+ * a camera (the schedule, and with it the map, depends on the scene); renders nothing.
+ * xrt_test_camlist above is not affected by the map: its lists are always built under the
+ * row-major one, slot s = pixel s, whatever p's flags say. */
+int xrt_test_slot_map(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""tools/wave_timeline.py FILE [--launch N] [--simds 1024] — the wave timeline of the merged step kernels.
+"""tools/wave_timeline.py FILE [--launch N] [--simds 1024] [--cost-map] — the wave timeline of the merged step kernels.
 
 FILE is what an experiment build with -DXRT_PHASE_CLOCK=1 writes for a render when XRT_WAVE_CLOCK_OUT
 names it (step_tri.hip, wave_clock_dump): per wave the launch's group argument (all ones: a launch
@@ -11,7 +11,15 @@ mid-frame launch (--launch, default the middle one of the first stream) the hist
 times, the histogram of wave durations and the resident waves over the launch's time; then the
 resident waves per SIMD over the middle half of the frame, all streams together — waves' summed
 residence inside the window over window x SIMDs, the figure SQ_WAVE_CYCLES x 4 / (time x clock x
-SIMDs) estimates from counters."""
+SIMDs) estimates from counters.
+
+--cost-map adds, per group stream, where the wave time of its mid-frame launches (the middle half
+of them) goes: the mean wave duration per partition — block b of a group's launch serves the
+group's partition b % its partition count (step_groups.h), and under the row-major slot map a
+partition is a band of image rows — with the spread of those means, the spread of wave durations
+inside a launch, and the correlation of a block's mean wave duration between consecutive launches
+(Pearson, over the blocks both launches have; the mean over the mid-frame pairs): near 1 when the
+same blocks are the slow ones round after round, near 0 when a wave's cost is chance."""
 import argparse
 
 import numpy as np
@@ -44,11 +52,64 @@ def resident(t0, t1, lo, hi, bins):
     return edges, out
 
 
+def group_part(G, g, lp):
+    """step_groups.h step_group_part"""
+    return ((lp >> 3) * G + g) * 8 + (lp & 7)
+
+
+def block_means(w):
+    """per block of one launch: mean wave duration in wall ticks (index = block)"""
+    b = w["block"].astype(np.int64)
+    d = (w["wall1"] - w["wall0"]).astype(np.float64)
+    n = np.bincount(b)
+    return np.bincount(b, weights=d) / np.maximum(n, 1), n > 0
+
+
+def cost_map(streams, us):
+    for tag in sorted(streams):
+        s, L = streams[tag]
+        nl = len(L) - 1
+        if tag == 0xFFFFFFFF or nl < 8:
+            continue
+        g, G, parts = tag & 15, (tag >> 4) & 15, tag >> 8
+        mid = range(nl // 4, nl - nl // 4)
+        print(f"\ncost map, group {g} of {G} ({parts} partitions), launches {mid[0]}..{mid[-1]} of {nl}:")
+        psum, pn = np.zeros(parts), np.zeros(parts)
+        ratio, cv, corr = [], [], []
+        prev = None
+        for k in mid:
+            w = s[L[k]:L[k + 1]]
+            d = (w["wall1"] - w["wall0"]).astype(np.float64) * us
+            lp = w["block"].astype(np.int64) % parts
+            psum += np.bincount(lp, weights=d, minlength=parts)
+            pn += np.bincount(lp, minlength=parts)
+            ratio.append(float(np.percentile(d, 99) / np.median(d)))
+            cv.append(float(d.std() / d.mean()))
+            cur = block_means(w)
+            if prev is not None:
+                m = min(len(cur[0]), len(prev[0]))
+                both = cur[1][:m] & prev[1][:m]
+                if both.sum() > 2:
+                    corr.append(float(np.corrcoef(cur[0][:m][both], prev[0][:m][both])[0, 1]))
+            prev = cur
+        pm = psum / np.maximum(pn, 1)
+        print(f"  wave durations inside a launch: 99th percentile / median {np.mean(ratio):.2f}, "
+              f"standard deviation / mean {np.mean(cv):.3f} (means over the launches)")
+        print(f"  block's mean wave duration, launch k against k + 1: correlation {np.mean(corr):.3f} "
+              f"(min {np.min(corr):.3f}, max {np.max(corr):.3f}, {len(corr)} pairs)")
+        print(f"  mean wave duration per partition: min {pm.min():.0f} us, mean {pm.mean():.0f} us, max {pm.max():.0f} us, "
+              f"max / min {pm.max() / pm.min():.2f}")
+        print("  partition (group-local -> global): mean wave duration us")
+        for lp0 in range(0, parts, 8):
+            print("   " + "  ".join(f"{group_part(G, g, lp):3d}:{pm[lp]:5.0f}" for lp in range(lp0, min(lp0 + 8, parts))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("file")
     ap.add_argument("--launch", type=int, default=None)
     ap.add_argument("--simds", type=int, default=1024)
+    ap.add_argument("--cost-map", action="store_true")
     a = ap.parse_args()
     head = np.fromfile(a.file, dtype="<u4", count=2)
     n, khz = int(head[0]), int(head[1])
@@ -96,6 +157,8 @@ def main():
           f"{inside / (m1 - m0) / a.simds:.2f}")
     whole = float((r["wall1"] - r["wall0"]).sum()) / (f1 - f0) / a.simds
     print(f"over the whole of it: {whole:.2f}")
+    if a.cost_map:
+        cost_map(streams, us)
 
 
 if __name__ == "__main__":

@@ -37,6 +37,7 @@ XRT_FLAG_DEEP_SINGLE, XRT_FLAG_DEEP_QUAD, XRT_FLAG_NO_PIXEL = 32, 64, 128
 XRT_FLAG_NO_SPEC = 256
 XRT_FLAG_WHITTED_BVH = 512
 XRT_FLAG_NO_OVERLAP = 1024
+XRT_FLAG_INTERLEAVE, XRT_FLAG_NO_INTERLEAVE = 2048, 4096
 XRT_SCHED_WAVEFRONT, XRT_SCHED_STEP, XRT_SCHED_STEP_TRI, XRT_SCHED_STEP_MERGED, XRT_SCHED_STEP_BVH = 0, 1, 2, 3, 4
 XRT_SCHED_PIXEL, XRT_SCHED_WHITTED, XRT_SCHED_WHITTED_BVH = 5, 6, 7
 XRT_SCHED_AOV = 8
@@ -225,6 +226,7 @@ SIGNATURES = {
     "xrt_test_whitted_math": (C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
     "xrt_test_fastdiv": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_uint64), u32p]),
     "xrt_test_camlist": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
+    "xrt_test_slot_map": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
 }
 
 _lib = None

@@ -75,7 +75,8 @@ __device__ __forceinline__ void aov_pixels(const KParams& P, const AovOut& A, co
         if (lane == 0) s = atomicAdd(work, 1u);
         s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
         if (s >= P.n_slots) break;   // every wave reaches this: the grid drains
-        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel_rowmajor(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         // the seeded state x[0..623] (k_seed) -> the circular buffer, 16 B per lane and load
         {
             const u32x4* src = reinterpret_cast<const u32x4*>(P.ring + (size_t)s * kRing);

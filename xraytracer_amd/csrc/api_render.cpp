@@ -188,6 +188,7 @@ KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* f
     bind_slots(c, P);
     P.fb = fb;
     P.camlist = nullptr;
+    P.slot_mul = 0;   // the row-major map, unless the render's plan interleaves (plan_render)
     return P;
 }
 
@@ -231,6 +232,7 @@ struct RenderPlan {
     bool pixel, fused, merged, two_level, step_tri, spec, camlist, elide, whitted, whitted_bvh;
     uint32_t n_part, part_cap;                     // live-list partitions
     uint32_t groups;                               // partition groups of the merged schedule's full-wave launches (1: none)
+    uint32_t slot_mul;                             // the slot -> pixel map (slot_map.h): 0 row-major, else interleaved
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
     uint64_t cap_iters;                            // loop iterations at most
@@ -292,6 +294,16 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom
     R.groups = R.merged && !R.two_level && !R.pixel && !R.whitted && !(p->flags & XRT_FLAG_NO_OVERLAP)
                    ? step_groups_for(R.n_part, XRT_STEP_GROUPS)
                    : 1u;
+    // pixels interleaved across slots (slot_map.h), so the waves of a launch cost about alike: the
+    // merged schedule — one-level shards from kSlotInterleaveMin slots on, two-level ones that start in
+    // the whole-wave layout (the sizes measured, tuning.h).  The flags force it on, for a merged render
+    // of any size, or off; every other schedule's kernels know the row-major map only
+    const bool can_interleave = R.merged && !R.pixel && !R.whitted && !(p->flags & XRT_FLAG_NO_INTERLEAVE);
+    const bool auto_interleave = XRT_SLOT_INTERLEAVE && (R.two_level ? n >= kBvhLive64 && step_merged_spw(P, n) == 64
+                                                                     : n >= kSlotInterleaveMin);
+    const char* ei = exp_env("XRT_INTERLEAVE");   // experiment builds only: 1 as XRT_FLAG_INTERLEAVE, 0 as NO_INTERLEAVE
+    const bool want_interleave = ei ? std::atoi(ei) != 0 : ((p->flags & XRT_FLAG_INTERLEAVE) || auto_interleave);
+    R.slot_mul = can_interleave && want_interleave ? slot_multiplier((uint32_t)n) : 0u;
     // segments per slot per step launch: kMergedVisits / kStepVisits unless the caller sets
     // visits_per_launch (results do not depend on it)
     const uint32_t draws = step_merged_draws(P);
@@ -610,7 +622,7 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     }
     const RenderPlan R = plan_render(P, p, d_var ? as<float2>(c->mom) : nullptr);
     if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
-    P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep;
+    P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep, P.slot_mul = R.slot_mul;
     const size_t lcap = (size_t)P.n_part * P.part_cap;
     const LiveLists L{{as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap}, as<uint32_t>(c->counts)};
     P.req = as<uint32_t>(c->lists) + 2 * lcap;
@@ -694,6 +706,26 @@ int xrt_render_device_after(xrt_ctx* c, const xrt_render_params* p, float* d_rgb
     if (!d_rgb_out) return set_err(c, XRT_ERR_INVALID, "null output");
     if (c && !c->subs.empty()) return render_multi(c, p, d_rgb_out, nullptr, st, 2, (hipStream_t)hip_stream);
     return render_impl(c, p, d_rgb_out, nullptr, st, 2, (hipStream_t)hip_stream);
+}
+
+// the slot -> pixel map the render of p would use, through the kernels' own device function
+int xrt_test_slot_map(xrt_ctx* c, const xrt_render_params* p, uint32_t* out) {
+    c = first_device(c);
+    if (!c || !p || !out) return XRT_ERR_INVALID;
+    int rc = check_render(c, p);
+    if (rc) return rc;
+    const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;
+    if (n == 0) return XRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d;
+    if ((rc = ensure(c, d, n * sizeof(uint32_t)))) return rc;
+    KParams P = render_params(c, p, n, nullptr);
+    P.slot_mul = plan_render(P, p, nullptr).slot_mul;
+    hipError_t e = launch_test_slot_map(P, as<uint32_t>(d), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    free_buf(d);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_slot_map");
 }
 
 // ---------------------------------------------------------- variance render ----

@@ -1,6 +1,6 @@
 // frame.hip — the kernels around a frame's path work, whatever the schedule: k_seed (the
 // per-pixel RNG streams and the first slot list), k_finish (the division by the sample count
-// and the counter reduction), k_finish_var (a variance render's plane) and k_tonemap (gamma and 8-bit quantisation), with their launchers.
+// and the counter reduction), k_finish_var (a variance render's plane), k_test_slot_map and k_tonemap (gamma and 8-bit quantisation), with their launchers.
 #include "launch.h"
 #include "path_common.h"
 
@@ -19,8 +19,8 @@ __global__ __launch_bounds__(kBlock) void k_seed(KParams P, uint32_t* list, uint
     const bool valid = s < P.n_slots;
     uint32_t row = 0, col = 0;
     if (valid) {
-        col = s % P.width;
-        row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel(P, s);
+        col = pix.col, row = pix.row;
     }
     uint32_t x = col + P.width * row;  // seed j + width * i
     for (uint32_t q = 0; q < kMT; q += 64) {
@@ -69,7 +69,8 @@ __global__ __launch_bounds__(kBlock) void k_finish(KParams P) {
     unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
     const float n = (float)P.spp;
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < P.n_slots; s += gridDim.x * kBlock) {
-        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         px[0] = px[0] / n, px[1] = px[1] / n, px[2] = px[2] / n;
         a[0] += P.c_seg[s];
@@ -100,13 +101,24 @@ __global__ __launch_bounds__(kBlock) void k_finish(KParams P) {
 __global__ __launch_bounds__(kBlock) void k_finish_var(KParams P, const float2* __restrict__ mom, float* __restrict__ var) {
     const float n = (float)P.spp;
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < P.n_slots; s += gridDim.x * kBlock) {
-        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         const float2 m = mom[s];
         const float mean = m.x / n;
         float v = m.y / n - mean * mean;
         v = v > 0.0f ? v : 0.0f;
         var[(size_t)col + (size_t)P.width * row] = v / (float)(P.spp - 1u);
     }
+}
+
+// ============================================================ k_test_slot_map ====
+// xrt_test_slot_map: every slot's pixel index, from the function the kernels above and the merged
+// schedule's call.
+__global__ __launch_bounds__(kBlock) void k_test_slot_map(KParams P, uint32_t* __restrict__ out) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= P.n_slots) return;
+    const SlotPixel pix = slot_pixel(P, s);
+    out[s] = pix.col + P.width * pix.row;
 }
 
 // ===================================================================== output ====
@@ -139,6 +151,11 @@ hipError_t launch_finish(const KParams& P, hipStream_t st) {
 hipError_t launch_finish_var(const KParams& P, const float2* mom, float* var, hipStream_t st) {
     const uint32_t blocks = std::min<uint32_t>((P.n_slots + kBlock - 1) / kBlock, 2048u);
     hipLaunchKernelGGL(k_finish_var, dim3(blocks), dim3(kBlock), 0, st, P, mom, var);
+    return hipGetLastError();
+}
+
+hipError_t launch_test_slot_map(const KParams& P, uint32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_test_slot_map, dim3((P.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, P, out);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "slot_map.h"
 #include "step_groups.h"
 #include "wavefront.h"
 
@@ -69,6 +70,8 @@ hipError_t launch_finish(const KParams& P, hipStream_t st);
 // a variance render's plane: the slots' {s1, s2} records (k_shade / k_whitted with a `mom`) into
 // var [height][width], the shard's pixels only (xrt_render_var's last five operations)
 hipError_t launch_finish_var(const KParams& P, const float2* mom, float* var, hipStream_t st);
+// out[s] = col + width * row of slot s under P's slot -> pixel map (xrt_test_slot_map)
+hipError_t launch_test_slot_map(const KParams& P, uint32_t* out, hipStream_t st);
 // Image::gammaCorrection + writePPM quantisation of n floats into n bytes
 hipError_t launch_tonemap(const float* rgb, uint32_t n, float inv_gamma, uint8_t* out, hipStream_t st);
 

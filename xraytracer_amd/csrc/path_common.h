@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
+#include "slot_map.h"
 #include "step_groups.h"
 #include "wavefront.h"
 #include "xrt.h"
@@ -16,6 +17,18 @@ namespace xrt {
 constexpr int kBlock = 256;
 constexpr int kTriTile = 512;    // triangles per LDS tile (24 KiB)
 constexpr int kSphTile = 1024;   // spheres per LDS tile (16 KiB + 4 KiB)
+
+// ===================================================================== slot -> pixel ====
+// The pixel of slot s (slot_map.h).  slot_pixel follows the render's map (KParams::slot_mul): the
+// kernels of the merged schedule and the ones around every frame (k_seed, k_camlist, k_finish*).
+// slot_pixel_rowmajor is the same map with the multiplier known to be 0 at compile time, for the
+// kernels of the schedules plan_render never interleaves.
+__device__ __forceinline__ SlotPixel slot_pixel(const KParams& P, uint32_t s) {
+    return slot_pixel_at(s, P.slot_mul, P.n_slots, P.width, P.shard_index, P.shard_count);
+}
+__device__ __forceinline__ SlotPixel slot_pixel_rowmajor(const KParams& P, uint32_t s) {
+    return slot_pixel_at(s, 0u, P.n_slots, P.width, P.shard_index, P.shard_count);
+}
 
 // ============================================================================ RNG ====
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {

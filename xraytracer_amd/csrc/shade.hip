@@ -290,7 +290,8 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
                     if (radiance_invalid(r)) {
                         ++nrej;
                     } else {
-                        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+                        const SlotPixel pix = slot_pixel_rowmajor(P, s);
+                        const uint32_t col = pix.col, row = pix.row;
                         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
                         px[0] = px[0] + r.x, px[1] = px[1] + r.y, px[2] = px[2] + r.z;
                         if (MOM) {   // s1 = s1 + l, s2 = s2 + l * l (include/xrt.h, xrt_render_var)
@@ -309,7 +310,8 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
                 }
                 // regenerate: jitter draws, camera ray (sample_start, path_common.h, open-coded here
                 // and below: the call adds SGPR spills)
-                const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+                const SlotPixel pix = slot_pixel_rowmajor(P, s);
+                const uint32_t col = pix.col, row = pix.row;
                 const float u = div_w(P, (float)(int)col + rng.next());
                 const float v = div_h(P, (float)(int)row + rng.next());
                 camera_ray(P, u, v, o, d);
@@ -327,7 +329,8 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
             if (st & ST_REGEN) {   // very first sample of the slot
                 st &= ~ST_REGEN;
                 if (MOM) mom[s] = make_float2(0.0f, 0.0f);
-                const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+                const SlotPixel pix = slot_pixel_rowmajor(P, s);
+                const uint32_t col = pix.col, row = pix.row;
                 const float u = div_w(P, (float)(int)col + rng.next());
                 const float v = div_h(P, (float)(int)row + rng.next());
                 camera_ray(P, u, v, o, d);

@@ -92,7 +92,8 @@ __device__ __forceinline__ v3 qsel3(v3 v, int src_lane) {
 __global__ __launch_bounds__(kBlock) void k_camlist(KParams P, uint32_t retire) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= P.n_slots) return;
-    const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+    const SlotPixel pix = slot_pixel(P, s);
+    const uint32_t col = pix.col, row = pix.row;
     const float m = 0.01f;
     const float u0 = ((float)col - m) / P.fw, u1 = ((float)col + (1.0f + m)) / P.fw;
     const float v0 = ((float)row - m) / P.fh, v1 = ((float)row + (1.0f + m)) / P.fh;
@@ -269,7 +270,8 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_spec(
         RngRegs<NW> rng;
         rng.c = 0;
         const uint32_t* ring = P.ring + (size_t)s * kRing;
-        const uint32_t col = s % width, row = P.shard_index + P.shard_count * (s / width);
+        const SlotPixel pix = slot_pixel(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)width * row);
         uint64_t cm = 0;    // the pixel's camera list
         int cov = -1;

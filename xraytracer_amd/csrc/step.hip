@@ -44,7 +44,8 @@ __global__ __launch_bounds__(BS, WV) void k_step(KParams P, const uint32_t* __re
             o = xyz(P.ray_o[s]), d = xyz(P.ray_d[s]);
         }
         uint32_t nseg = 0, nsh = 0, nrej = 0, nstall = 0;
-        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel_rowmajor(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         v3 acc = mk(px[0], px[1], px[2]);   // the pixel's running sum, in registers this launch
         rng.prefetch(g - rng.c);
@@ -444,7 +445,8 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_tri(const KPara
         uint32_t g = 0, depth = 0, k = 0;
         Rng rng{P.ring + (size_t)s * kRing, 0};
         v3 thr = mk(1, 1, 1), rad = mk(0, 0, 0), o = mk(0, 0, 0), d = mk(0, 0, 0), acc = mk(0, 0, 0);
-        const uint32_t col = s % P.width, row = P.shard_index + P.shard_count * (s / P.width);
+        const SlotPixel pix = slot_pixel_rowmajor(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         if (live) slot_load(P, s, st, px, g, rng, depth, k, thr, rad, o, d, acc);
         uint32_t nseg = 0, nsh = 0, nrej = 0;

@@ -588,7 +588,8 @@ __device__ __forceinline__ void step_merged_body(
         for (int l = 0; l <= NL; ++l) so[l] = sd[l] = c1[l] = c0[l] = mk(0, 0, 0), stm[l] = 0.0f;
         uint32_t shm = 0;          // shadow rays in flight (bit per light)
         bool ext = false, fin = false;
-        const uint32_t col = s % width, row = P.shard_index + P.shard_count * (s / width);
+        const SlotPixel pix = slot_pixel(P, s);
+        const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)width * row);
         if (live) {
             g = glb<gu32>(P.rng_g)[s];

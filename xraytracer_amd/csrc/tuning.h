@@ -34,6 +34,12 @@
 #ifndef XRT_STEP_GROUPS
 #define XRT_STEP_GROUPS 2    // k_step_merged's full-wave launches of one-level scenes in this many partition groups, each on a stream of its own (1..3; step_groups.h; C2 66.4 -> 51.5 ms; 3: 83.7 ms; 1: one launch per round, the former sequence, 66.2 ms)
 #endif
+#ifndef XRT_SLOT_INTERLEAVE
+#define XRT_SLOT_INTERLEAVE 1    // merged renders interleave pixels across slots (slot_map.h; C2 51.6 -> 45.6 ms): one-level shards of at least XRT_SLOT_INTERLEAVE_MIN slots, two-level ones that start in whole waves (XRT_BVH_LIVE64); 0: only under XRT_FLAG_INTERLEAVE
+#endif
+#ifndef XRT_SLOT_INTERLEAVE_MIN
+#define XRT_SLOT_INTERLEAVE_MIN 60000   // ... the smallest one-level shard that does: C2 shard 0 of 8 (60,000 slots, 16-slot layout) 22.96 -> 22.17 ms forced; smaller shards are not measured and stay row-major
+#endif
 #ifndef XRT_KSTEP_LDS_REFILL
 #define XRT_KSTEP_LDS_REFILL 2   // k_step in-line refill staged through LDS: 1 always, 2 except sphere-BVH scenes, 0 never
 #endif

@@ -5,8 +5,8 @@
 //   scene  : triangles as 3 float4 per triangle {(v0, obj), (e1 = v1-v0, occluder), (e2 = v2-v0, 0)}
 //            in Scene::m_objects order, plus per-triangle ng and vertex normals read only
 //            at shading; spheres {(c, r)}; boxes {pmin, pmax}; object and light tables.
-//   slots  : one path slot per pixel of this shard; all per-slot state is SoA (float4 /
-//            uint32 arrays indexed by slot) so a wave's loads are coalesced.
+//   slots  : one path slot per pixel of this shard (which one: slot_map.h); all per-slot state is
+//            SoA (float4 / uint32 arrays indexed by slot) so a wave's loads are coalesced.
 //   RNG    : per slot a 1248-word ring (two 624-word mt19937 blocks) + cursor/generated
 //            counters.  k_seed writes each slot's seeded state and one k_refill launch
 //            twists its first block; after that every schedule twists a slot's next block
@@ -39,6 +39,7 @@ constexpr uint32_t kStepVisits = 32; // fused schedule: path segments per slot p
 constexpr uint32_t kMergedVisits = 64; // merged-trace schedule: segments per slot per launch (at most;
                                        // clamped so a launch's draws fit one refill block)
 constexpr uint32_t kMergedLive64 = 160000;  // merged-trace schedule: live slots for 64 slots per wave
+constexpr uint32_t kSlotInterleaveMin = XRT_SLOT_INTERLEAVE_MIN;   // merged one-level schedule: slots of a shard for the interleaved slot map
 constexpr uint32_t kMergedLive32 = XRT_LIVE32;   // ... and for 32 (below: 16 slots, 4 lanes each)
 constexpr uint32_t kBvhLive64 = XRT_BVH_LIVE64;   // two-level merged schedule: 64 slots per wave above this
 constexpr uint32_t kBvhLive32 = XRT_BVH_LIVE32;   // ... 32 above this, else 16
@@ -248,6 +249,7 @@ struct KParams {
     // ---- render
     int integrator;
     uint32_t max_depth, width, height, spp, shard_index, shard_count, n_slots;
+    uint32_t slot_mul;           // slot -> pixel map (slot_map.h): 0 row-major, else the interleaving multiplier
     uint32_t n_part, part_cap;   // live-list partitions: n_part (<= kMaxParts) of part_cap slots
     uint32_t rng_keep;           // fused schedule refill threshold (words ahead)
     uint32_t spw_req;            // merged schedule: requested slots per wave (0 = by live count)

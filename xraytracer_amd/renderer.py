@@ -70,7 +70,7 @@ class HipRenderer:
 
     def params(self, scene, width, height, shard_index=0, shard_count=1, timing=False, integrator=None,
                max_depth=None, schedule="auto", slots_per_wave=0, visits_per_launch=0, group=True,
-               accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True):
+               accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True, interleave=None):
         """schedule: "auto" (fused k_step when the scene fits in LDS — for small triangle
         scenes with merged shadow + extension traces, for Direct / Normal pixel-parallel
         sample chains (k_pixel) — else the multi-pass wavefront), "step" (the per-slot fused
@@ -87,7 +87,10 @@ class HipRenderer:
         not fit LDS through its triangle BVH (XRT_FLAG_WHITTED_BVH, XRT_SCHED_WHITTED_BVH) instead
         of refusing it; a scene that fits LDS renders as without it.  overlap: the merged schedule's
         full-wave step launches run in partition groups on streams of their own (overlap=False sets
-        XRT_FLAG_NO_OVERLAP: one launch per round); results never depend on it."""
+        XRT_FLAG_NO_OVERLAP: one launch per round); results never depend on it.  interleave: pixels
+        interleaved across the merged schedule's path slots (None: the library's rule, large one-level
+        renders; True sets XRT_FLAG_INTERLEAVE, any merged render; False sets XRT_FLAG_NO_INTERLEAVE);
+        results never depend on it."""
         if schedule not in ("auto", "step", "wavefront", "step_tri"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if deep not in ("auto", "single", "quad"):
@@ -102,6 +105,7 @@ class HipRenderer:
                    (abi.XRT_FLAG_NO_PIXEL if schedule in ("step", "step_tri") else 0) |
                    (abi.XRT_FLAG_ACCUMULATE if accumulate else 0) | (0 if spec else abi.XRT_FLAG_NO_SPEC) |
                    (abi.XRT_FLAG_WHITTED_BVH if whitted_bvh else 0) | (0 if overlap else abi.XRT_FLAG_NO_OVERLAP) |
+                   (0 if interleave is None else abi.XRT_FLAG_INTERLEAVE if interleave else abi.XRT_FLAG_NO_INTERLEAVE) |
                    {"auto": 0, "single": abi.XRT_FLAG_DEEP_SINGLE, "quad": abi.XRT_FLAG_DEEP_QUAD}[deep])
         p.slots_per_wave, p.visits_per_launch = slots_per_wave, visits_per_launch
         return p
@@ -340,13 +344,24 @@ class HipRenderer:
 
     def camlist(self, scene: SceneBundle, width: int, height: int, shard_index: int = 0, shard_count: int = 1):
         """The camera lists the speculative merged schedule builds for the shard (xrt_test_camlist, a
-        device self-test): (slots, 4) uint32 in slot order — list bits 0-31, bits 32-63, the
+        device self-test): (slots, 4) uint32 in pixel order, slot s = pixel s of the shard, whatever
+        map a render uses — list bits 0-31, bits 32-63, the
         covering triangle or 0xffffffff, 0."""
         if self._uploaded is not scene:
             self.upload(scene)
         p = self.params(scene, width, height, shard_index=shard_index, shard_count=shard_count)
         out = np.zeros((len(range(shard_index, height, shard_count)) * width, 4), np.uint32)
         self._check(self._lib.xrt_test_camlist(self.ctx, C.byref(p), abi.u32ptr(out)), "xrt_test_camlist")
+        return out
+
+    def slot_map(self, scene: SceneBundle, width: int, height: int, **kw) -> np.ndarray:
+        """The slot -> pixel map a render with these arguments (those of params) would use
+        (xrt_test_slot_map, a device self-test): per slot of the shard its pixel index col + width * row."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        out = np.zeros(len(range(p.shard_index, height, p.shard_count)) * width, np.uint32)
+        self._check(self._lib.xrt_test_slot_map(self.ctx, C.byref(p), abi.u32ptr(out)), "xrt_test_slot_map")
         return out
 
     def tonemap(self, width: int, height: int, gamma: float, device_ptr: int = 0) -> np.ndarray:
