@@ -6,6 +6,9 @@
 // sample count (at least 2).  Both frames go through gammaCorrection(1.2) and writePPM.
 //
 //   render_var [width height spp out_prefix]     -> out_prefix.noisy.ppm, out_prefix.denoised.ppm
+//   render_var width height spp out_prefix fused -> the same two files through the fused schedule
+//       (renderVariance's last argument, XRT_FLAG_VAR_FUSED: same frame and plane), and the frame and the
+//       plane as they were rendered, raw float32: out_prefix.frame.raw, out_prefix.variance.raw
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -38,6 +41,7 @@ int main(int argc, char** argv) {
     const uint32_t height = argc > 2 ? (uint32_t)atoi(argv[2]) : 585;
     const uint32_t n_samples = argc > 3 ? (uint32_t)atoi(argv[3]) : 4;
     const std::string out = argc > 4 ? argv[4] : "render_var";
+    const bool fused = argc > 5 && std::string(argv[5]) == "fused";
     const uint32_t max_depth = 3;
 
     const float aspect_ratio = static_cast<float>(width) / height;
@@ -57,10 +61,20 @@ int main(int argc, char** argv) {
     auto renderer = std::make_unique<HipRenderer>(n_samples, camera.get(), integrator.get());
     Image image(width, height);
     std::vector<float> variance;
-    renderer->renderVariance(scene, Sampler::SamplerType::Uniform, image, variance);
+    renderer->renderVariance(scene, Sampler::SamplerType::Uniform, image, variance, fused);
     if (renderer->lastStatus() != 0) {
         std::fprintf(stderr, "renderVariance failed: %s\n", renderer->lastError().c_str());
         return 2;
+    }
+    if (fused) {
+        std::printf("schedule %llu\n", (unsigned long long)renderer->lastStats().schedule);
+        FILE* ff = std::fopen((out + ".frame.raw").c_str(), "wb");
+        FILE* fv = std::fopen((out + ".variance.raw").c_str(), "wb");
+        const bool ok = ff && fv && std::fwrite(image.data(), sizeof(float), 3 * variance.size(), ff) == 3 * variance.size() &&
+                        std::fwrite(variance.data(), sizeof(float), variance.size(), fv) == variance.size();
+        if (ff) std::fclose(ff);
+        if (fv) std::fclose(fv);
+        if (!ok) return 3;
     }
     double mean_sample_variance = 0.0;
     for (float v : variance) mean_sample_variance += v;

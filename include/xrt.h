@@ -190,6 +190,9 @@ enum {
                                    same results                                                 */
     XRT_FLAG_NO_INTERLEAVE = 4096u, /* ... and this one keeps every render on the row-major map
                                    (slot s = pixel s); it wins over XRT_FLAG_INTERLEAVE          */
+    XRT_FLAG_VAR_FUSED = 8192u, /* xrt_render_var / xrt_render_var_device only: the path integrators
+                                   keep the fused or merged schedule instead of the wavefront (see
+                                   there); every other entry point ignores it; same results      */
     XRT_FLAG_ACCUMULATE = 16u  /* Renderer::render's in-place contract (Src/renderer.cpp:75,98):
                                   each owned pixel starts from the value already in the output
                                   buffer (Image::addPixel adds to it in sample order), then
@@ -371,6 +374,15 @@ int  xrt_render_device_after(xrt_ctx* ctx, const xrt_render_params* p, float* d_
  * flags, slots_per_wave and visits_per_launch are checked as xrt_render checks them and have no
  * effect.  XRT_FLAG_TIMING works.  Every xrt_stats field is what xrt_render reports for the same
  * p with XRT_FLAG_WAVEFRONT set (the plane's kernel runs and is timed under XRT_K_FINISH).
+ * With XRT_FLAG_VAR_FUSED the six path integrators instead run the schedule xrt_render chooses for
+ * p with XRT_FLAG_NO_SPEC | XRT_FLAG_NO_PIXEL added (the speculative and the pixel-parallel kernels
+ * sum no moments): every other schedule flag, slots_per_wave and visits_per_launch then count as
+ * they do for xrt_render.  The frame and the plane are bit for bit those of the call without the
+ * flag — the arithmetic above is the whole contract — and every xrt_stats field is what xrt_render
+ * reports for p | XRT_FLAG_NO_SPEC | XRT_FLAG_NO_PIXEL; the plane's kernel stays under
+ * XRT_K_FINISH.  Where that schedule is the wavefront (the scene does not fit the fused schedule,
+ * or XRT_FLAG_WAVEFRONT is set) and for WhittedIntegrator the call is the one without the flag.
+ * The refusals do not change.
  * A multi-device context shards rows as for a render and assembles both planes on devices[0].
  * After the call the context's last framebuffer — what xrt_tonemap and the filters read for a
  * NULL colour — is this frame, for the device entry point too. */

@@ -78,8 +78,10 @@ public:
     // beside the frame, the variance of each pixel's mean luminance from the pixel's own samples
     // (xrt.h, xrt_render_var; n_samples must be at least 2): `variance` is resized to width *
     // height in Image::pixels order.  It is what denoiseVar takes as variance_in.  Errors as
-    // render() reports them.
-    void renderVariance(const Scene& scene, Sampler::SamplerType st, Image& image, std::vector<float>& variance) const;
+    // render() reports them.  fused: the path integrators keep the fused or merged schedule instead
+    // of the wavefront (XRT_FLAG_VAR_FUSED); the same frame and plane, sooner.
+    void renderVariance(const Scene& scene, Sampler::SamplerType st, Image& image, std::vector<float>& variance,
+                        bool fused = false) const;
     // The guide buffers of the frame render() would make of `scene` with this camera and
     // n_samples (the integrator is not consulted); errors as render() reports them.
     void renderGuides(const Scene& scene, GuideImages& guides) const;

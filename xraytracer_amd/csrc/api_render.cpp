@@ -237,7 +237,8 @@ struct RenderPlan {
     uint64_t poll_every, ahead;                    // LivePoll cadence
     uint64_t cap_iters;                            // loop iterations at most
     // a variance render (xrt_render_var): the slots' {s1, s2} records, which select the moments
-    // builds of k_shade / k_whitted / k_whitted_bvh; null for a plain render
+    // builds of k_shade / k_whitted / k_whitted_bvh and, under XRT_FLAG_VAR_FUSED, of k_step /
+    // k_step_tri / k_step_merged; null for a plain render
     float2* mom;
 };
 
@@ -502,8 +503,11 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
         if (groups > 1) {
             if ((rc = GS.fork())) return rc;
             for (uint32_t g = 0; g < groups; ++g) {
-                const hipError_t e = launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
-                                                        poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g]);
+                const hipError_t e =
+                    R.mom ? launch_step_merged_mom(P, dP, c->step_objs, list, ci, out, co, cz, R.mom, R.step_visits,
+                                                   poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g])
+                          : launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
+                                               poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g]);
                 if (e != hipSuccess) return hip_err(c, e, "k_step");
             }
             T.S.launches[XRT_K_STEP] += groups;
@@ -522,11 +526,14 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
         const hipError_t e = T.launch(XRT_K_STEP, [&] {
             if (spec_now)
                 return launch_step_spec(P, dP, list, ci, out, co, cz, R.spec_visits, poll.live_part_max, spw, c->stream);
+            if (R.merged && R.mom)
+                return launch_step_merged_mom(P, dP, c->step_objs, list, ci, out, co, cz, R.mom, R.step_visits,
+                                              poll.live_hint, poll.live_part_max, 1, 0, c->stream);
             if (R.merged)
                 return launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
                                           poll.live_hint, poll.live_part_max, 1, 0, c->stream);
             return launch_step(P, dP, list, ci, out, co, cz, L.req(1), R.step_visits, blocks, poll.live_hint, R.step_tri,
-                               c->stream);
+                               c->stream, R.mom);
         });
         if (e != hipSuccess) return hip_err(c, e, "k_step");
         if ((rc = poll.after(it, co))) return rc;
@@ -591,13 +598,19 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     int rc = check_render(c, p);
     if (rc) return rc;
     // A variance render is this render with its plan forced to the wavefront schedule (Whitted has
-    // one schedule anyway): no other schedule flag and no launch geometry reaches the plan.
+    // one schedule anyway): no other schedule flag and no launch geometry reaches the plan.  Under
+    // XRT_FLAG_VAR_FUSED it is this render without speculative starts and pixel-parallel chains,
+    // whose kernels have no moments build: the plan is xrt_render's for those flags.
     xrt_render_params forced;
     if (d_var) {
         if ((rc = check_render_var(c, p))) return rc;
         forced = *p;
-        forced.flags = (p->flags & (XRT_FLAG_TIMING | XRT_FLAG_WHITTED_BVH)) | XRT_FLAG_WAVEFRONT;
-        forced.slots_per_wave = forced.visits_per_launch = 0;
+        if ((p->flags & XRT_FLAG_VAR_FUSED) && !(p->flags & XRT_FLAG_WAVEFRONT) && p->integrator != XRT_INTEGRATOR_WHITTED) {
+            forced.flags = (p->flags & ~XRT_FLAG_VAR_FUSED) | XRT_FLAG_NO_SPEC | XRT_FLAG_NO_PIXEL;
+        } else {
+            forced.flags = (p->flags & (XRT_FLAG_TIMING | XRT_FLAG_WHITTED_BVH)) | XRT_FLAG_WAVEFRONT;
+            forced.slots_per_wave = forced.visits_per_launch = 0;
+        }
         p = &forced;
     }
     if ((rc = order_after(c, wait, wait_stream, false))) return rc;
@@ -643,6 +656,9 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
         HIPCHK(c, hipMemcpyAsync(fb, h_out, npix * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (d_var) HIPCHK(c, hipMemsetAsync(d_var, 0, npix * sizeof(float), c->stream));   // outside the shard: +0
     HIPCHK(c, hipMemsetAsync(P.stats, 0, 512, c->stream));
+    // the fused kernels' moments builds only add to the records (k_shade zeroes a record in the slot's
+    // first visit), and a pixel k_camlist retires is never loaded by one: its record stays {+0, +0}
+    if (R.mom && R.fused && !R.pixel) HIPCHK(c, hipMemsetAsync(R.mom, 0, n * sizeof(float2), c->stream));
     if ((rc = seed_paths(c, P, R, L, T))) return rc;
 
     // run, finish

@@ -151,10 +151,12 @@ void HipRenderer::render(const Scene& scene, Sampler::SamplerType, Image& image)
     if (rc != XRT_OK) fail(rc, std::string("xrt_render: ") + xrt_last_error(m_ctx));
 }
 
-void HipRenderer::renderVariance(const Scene& scene, Sampler::SamplerType, Image& image, std::vector<float>& variance) const {
+void HipRenderer::renderVariance(const Scene& scene, Sampler::SamplerType, Image& image, std::vector<float>& variance,
+                                 bool fused) const {
     xrt_render_params p;
     variance.assign((size_t)image.getWidth() * image.getHeight(), 0.0f);
     if (!renderInputs(scene, image, p)) return;
+    if (fused) p.flags |= XRT_FLAG_VAR_FUSED;
     const int rc = xrt_render_var(m_ctx, &p, image.data(), variance.data(), &m_stats);
     if (rc != XRT_OK) fail(rc, std::string("xrt_render_var: ") + xrt_last_error(m_ctx));
 }

@@ -103,9 +103,10 @@ bool use_step_tri(const KParams& P);   // triangle scene: k_step_tri (cooperativ
 // every schedule's step launch; only the seeding k_refill reads the request list)
 // dP: device copy of P (the triangle-scene kernel reads its parameters from memory)
 // tri: the caller's use_step_tri(P), decided once per render (k_step_tri instead of k_step)
+// mom: as launch_shade's (the moments builds of k_step / k_step_tri, XRT_FLAG_VAR_FUSED)
 hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count, uint32_t* out,
                        uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
-                       uint64_t live, bool tri, hipStream_t st);
+                       uint64_t live, bool tri, hipStream_t st, float2* mom = nullptr);
 
 // ------------------------------------------------------------------- step_tri.hip ----
 // twist the rings of the slots on P.req (count at *count); clears *zero_count
@@ -132,6 +133,12 @@ hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObj
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
                               uint32_t groups, uint32_t group, hipStream_t st);
+// ... and its moments builds (a unit of their own, step_tri.hip as step_tri_mom.o): the slots' {s1, s2}
+// records, as launch_shade's mom, in req_count's place
+hipError_t launch_step_merged_mom(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
+                                  const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
+                                  float2* mom, uint32_t visits, uint64_t live, uint32_t live_part_max,
+                                  uint32_t groups, uint32_t group, hipStream_t st);
 #if XRT_PHASE_CLOCK
 // experiment builds: the merged kernels' per-wave entry / exit clocks of the work queued on st so far,
 // written to `path` (null: dropped) and cleared; tools/wave_timeline.py reads the file

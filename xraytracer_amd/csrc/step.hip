@@ -4,6 +4,8 @@
 //   k_step_tri : small triangle scenes (GI / Direct) with cooperative traces (coop_trace)
 // The merged-trace triangle schedule (step_tri.hip) and its speculative variant (spec.hip)
 // take the scenes they are eligible for before these two.
+#include <type_traits>
+
 #include "launch.h"
 #include "lscene.h"
 #include "medium.h"
@@ -13,11 +15,17 @@ namespace xrt {
 
 // WV: waves per SIMD the register budget is sized for (XRT_KSTEP_WAVES; the volumetric
 // integrators also at 2, for launches with too few live slots to fill more: no spills)
-template <int SCN, int INTEG, int BS = kBlock, int WV = XRT_KSTEP_WAVES>
+// MOM (a variance render under XRT_FLAG_VAR_FUSED, xrt_render_var): an accepted sample also adds its
+// luminance l and l * l to the slot's record {s1, s2}, which arrives in req_count's place (no step
+// kernel reads req_count; k_shade<MOM>'s route, shade.hip) and was zeroed before seeding
+// (render_impl).  Every sample ends in the `while (ended)` block: the one site.  The record is
+// carried in registers for the launch, loaded and stored beside the pixel's sum (XRT_MOM_REGS,
+// tuning.h; 0: a read-modify-write at the site, measured 2-5 % slower).
+template <int SCN, int INTEG, int BS = kBlock, int WV = XRT_KSTEP_WAVES, bool MOM = false>
 __global__ __launch_bounds__(BS, WV) void k_step(KParams P, const uint32_t* __restrict__ list,
                                                   const uint32_t* __restrict__ count, uint32_t* __restrict__ out,
-                                                  uint32_t* out_count, uint32_t* zero_count, uint32_t* req_count,
-                                                  uint32_t visits) {
+                                                  uint32_t* out_count, uint32_t* zero_count,
+                                                  std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits) {
     extern __shared__ __attribute__((aligned(16))) f4 lds_step[];
     char* lb = reinterpret_cast<char*>(lds_step);
     const int tid = threadIdx.x;
@@ -48,6 +56,8 @@ __global__ __launch_bounds__(BS, WV) void k_step(KParams P, const uint32_t* __re
         const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         v3 acc = mk(px[0], px[1], px[2]);   // the pixel's running sum, in registers this launch
+        float2 msum = make_float2(0.0f, 0.0f);   // MOM with XRT_MOM_REGS: the slot's record, carried like acc
+        if constexpr (MOM && XRT_MOM_REGS) msum = req_count[s];
         rng.prefetch(g - rng.c);
         // VPT family: one event per iteration (kVptEvents) — a trace + surface interaction, or
         // ONE delta-tracking collision of a walk that continues across iterations in
@@ -249,6 +259,16 @@ __global__ __launch_bounds__(BS, WV) void k_step(KParams P, const uint32_t* __re
                     ++nrej;
                 } else {
                     acc = acc + r;
+                    if constexpr (MOM) {   // s1 = s1 + l, s2 = s2 + l * l (include/xrt.h, xrt_render_var)
+                        const float l = luminance(r);
+                        if constexpr (XRT_MOM_REGS) {
+                            msum.x = msum.x + l, msum.y = msum.y + l * l;
+                        } else {
+                            float2 m = req_count[s];
+                            m.x = m.x + l, m.y = m.y + l * l;
+                            req_count[s] = m;
+                        }
+                    }
                 }
                 ++k;
                 if (k >= P.spp) {
@@ -274,6 +294,7 @@ __global__ __launch_bounds__(BS, WV) void k_step(KParams P, const uint32_t* __re
         }
         // slot_store (path_common.h), open-coded as slot_load above
         px[0] = acc.x, px[1] = acc.y, px[2] = acc.z;
+        if constexpr (MOM && XRT_MOM_REGS) req_count[s] = msum;
         // RNG refill (words ahead < rng_keep <= 624): twisted by this wave below
         want_req = !(st & (ST_DONE | ST_RNGREQ)) && g - rng.c < P.rng_keep;
         P.state[s] = st;
@@ -402,12 +423,14 @@ __device__ __forceinline__ void coop_closest(const KParams& P, const LScene& L, 
 // k_step for triangle scenes (GI / Direct) with cooperative traces: the same per-slot
 // sequence as k_step, arranged so every trace is reached by the whole wave (per-lane
 // activity flags instead of divergent control flow around the traces).
-template <int INTEG>
+// MOM: as k_step's.
+template <int INTEG, bool MOM = false>
 __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_tri(const KParams* __restrict__ Pp,
                                                                       const uint32_t* __restrict__ list,
                                                                       const uint32_t* __restrict__ count,
                                                                       uint32_t* __restrict__ out, uint32_t* out_count,
-                                                                      uint32_t* zero_count, uint32_t* req_count,
+                                                                      uint32_t* zero_count,
+                                                                      std::conditional_t<MOM, float2*, uint32_t*> req_count,
                                                                       uint32_t visits) {
     // KParams lives in device memory here (one copy per render): fields are fetched with
     // scalar loads when needed instead of pinning ~150 SGPRs of kernel arguments
@@ -449,6 +472,10 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_tri(const KPara
         const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
         if (live) slot_load(P, s, st, px, g, rng, depth, k, thr, rad, o, d, acc);
+        float2 msum = make_float2(0.0f, 0.0f);   // MOM with XRT_MOM_REGS: the slot's record, carried like acc
+        if constexpr (MOM && XRT_MOM_REGS) {
+            if (live) msum = req_count[s];
+        }
         uint32_t nseg = 0, nsh = 0, nrej = 0;
         for (uint32_t vis = 0; vis < visits; ++vis) {
             const bool act = live && !(st & ST_DONE) && g - rng.c >= kRngVisit;
@@ -548,6 +575,16 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_tri(const KPara
                     ++nrej;
                 } else {
                     acc = acc + r;
+                    if constexpr (MOM) {
+                        const float l = luminance(r);
+                        if constexpr (XRT_MOM_REGS) {
+                            msum.x = msum.x + l, msum.y = msum.y + l * l;
+                        } else {
+                            float2 m = req_count[s];
+                            m.x = m.x + l, m.y = m.y + l * l;
+                            req_count[s] = m;
+                        }
+                    }
                 }
                 ++k;
                 if (k >= P.spp) {
@@ -566,6 +603,9 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_tri(const KPara
         }
         bool want_req = false;   // the slot's ring runs low: twisted below
         if (live) want_req = slot_store(P, s, st, px, g, rng, depth, k, thr, rad, o, d, acc, nseg, nsh, nrej, 0u);
+        if constexpr (MOM && XRT_MOM_REGS) {
+            if (live) req_count[s] = msum;
+        }
         wave_append(live && !(st & ST_DONE), s, out + it.p * P.part_cap, out_count + it.p, lane);
         // the wave's refills in-line through its trace scratch (idle now)
         static_assert(sizeof(CoopWave) >= kMT * sizeof(uint32_t), "refill staging");
@@ -596,15 +636,18 @@ bool use_step_tri(const KParams& P) {
            ((step_layout(P).total + 15u) & ~15u) + (kBlock / 64) * sizeof(CoopWave) <= kStepLds;
 }
 
-hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count, uint32_t* out,
-                       uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
-                       uint64_t live, bool tri, hipStream_t st) {
+// MOM: the moments builds, the slots' records in req_count's place
+template <bool MOM>
+static hipError_t launch_step_t(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count,
+                                uint32_t* out, uint32_t* out_count, uint32_t* zero,
+                                std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits, uint32_t blocks,
+                                uint64_t live, bool tri, hipStream_t st) {
     if (!step_lds_bytes(P)) return hipErrorInvalidValue;
     if (P.n_part == 0 || blocks % P.n_part != 0) return hipErrorInvalidValue;   // part_iter's grid contract
     if (tri) {   // use_step_tri: GI or Direct
         const size_t lds = ((step_layout(P).total + 15u) & ~15u) + (kBlock / 64) * sizeof(CoopWave);
         return with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {
-            hipLaunchKernelGGL((k_step_tri<decltype(integ)::value>), dim3(blocks), dim3(kBlock), lds, st, dP, list, count,
+            hipLaunchKernelGGL((k_step_tri<decltype(integ)::value, MOM>), dim3(blocks), dim3(kBlock), lds, st, dP, list, count,
                                out, out_count, zero, req_count, visits);
             return hipGetLastError();
         });
@@ -620,7 +663,7 @@ hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list
                     // the grid must stay a multiple of n_part (part_iter: block b serves partition b % n_part
                     // and chunk b / n_part of gridDim / n_part chunks)
                     const uint32_t chunks = std::max(1u, blocks / P.n_part);
-                    hipLaunchKernelGGL((k_step<SCN, I, 512>), dim3(P.n_part * ((chunks + 1) / 2)), dim3(512),
+                    hipLaunchKernelGGL((k_step<SCN, I, 512, XRT_KSTEP_WAVES, MOM>), dim3(P.n_part * ((chunks + 1) / 2)), dim3(512),
                                        kstep_lds_bytes(P, 512), st, P, list, count, out, out_count, zero, req_count, visits);
                     return hipGetLastError();
                 }
@@ -630,15 +673,22 @@ hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list
             // spilling (C5 shard 0 of 8: 43.9 -> 41.9 ms; a full frame stays at 4 waves per SIMD)
             if constexpr (I == XRT_INTEGRATOR_VPT || I == XRT_INTEGRATOR_VPT_NEE)
                 if (live < kVptLowLive) {
-                    hipLaunchKernelGGL((k_step<SCN, I, kBlock, 2>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out,
+                    hipLaunchKernelGGL((k_step<SCN, I, kBlock, 2, MOM>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out,
                                        out_count, zero, req_count, visits);
                     return hipGetLastError();
                 }
-            hipLaunchKernelGGL((k_step<SCN, I>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out, out_count, zero,
+            hipLaunchKernelGGL((k_step<SCN, I, kBlock, XRT_KSTEP_WAVES, MOM>), dim3(blocks), dim3(kBlock), lds, st, P, list, count, out, out_count, zero,
                                req_count, visits);
             return hipGetLastError();
         });
     });
+}
+
+hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list, const uint32_t* count, uint32_t* out,
+                       uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
+                       uint64_t live, bool tri, hipStream_t st, float2* mom) {
+    if (mom) return launch_step_t<true>(P, dP, list, count, out, out_count, zero, mom, visits, blocks, live, tri, st);
+    return launch_step_t<false>(P, dP, list, count, out, out_count, zero, req_count, visits, blocks, live, tri, st);
 }
 
 }  // namespace xrt

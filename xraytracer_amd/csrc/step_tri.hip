@@ -31,7 +31,13 @@
 //
 // GIIntegrator with maxDepth 0 and scenes with more than kMergedMaxObjs objects keep using
 // k_step_tri.
+//
+// This file is compiled twice (Makefile).  As step_tri.o it holds everything below but the moments
+// builds.  As step_tri_mom.o (-DXRT_STEP_MOM_UNIT) it holds the moments builds of the merged kernels
+// and their launcher, launch_step_merged_mom, alone: as many instantiations of the merged body again,
+// compiled beside the first unit instead of after it.
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 #include "bvh.h"
@@ -347,6 +353,7 @@ __host__ __device__ inline BvhStepLayout bvh_step_layout(const KParams& P, uint3
     return B;
 }
 
+#ifndef XRT_STEP_MOM_UNIT
 // ------------------------------------------------- two-level trace, phase A ----
 // k_trace_2a (trace.hip) with the small objects traced by merged_trace's object-major
 // pair passes instead of a per-lane object loop: one wave = 64 slots, their extension ray
@@ -393,6 +400,7 @@ hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const ui
         return hipGetLastError();
     });
 }
+#endif   // !XRT_STEP_MOM_UNIT
 
 // --------------------------------------------------------------- RNG refills ----
 // k_refill_merged: every slot's first twist (the seeding refill after k_seed; later twists
@@ -420,7 +428,7 @@ hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const ui
 // kernels records the constant-rate wall clock and the shader clock at entry and at exit, one
 // record per wave in launch order of arrival; render_impl writes the records of a render to the
 // file XRT_WAVE_CLOCK_OUT names (wave_clock_dump).  tag: the launch's group argument, ~0 ungrouped.
-#if XRT_PHASE_CLOCK
+#if XRT_PHASE_CLOCK && !defined(XRT_STEP_MOM_UNIT)   // the moments builds record no clocks
 constexpr uint32_t kWaveClockCap = 1u << 20;
 struct WaveClockRec {
     uint32_t tag, block;
@@ -473,12 +481,23 @@ struct WaveClock {
 
 // GROUPED: the launch serves one partition group (step_groups.h; grp: step_group_arg) — the body of
 // k_step_merged_group.  Without it the body of k_step_merged, every partition, grp unused.
-template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, bool GROUPED>
+//
+// MOM (a variance render under XRT_FLAG_VAR_FUSED, xrt_render_var): an accepted sample also adds its
+// luminance l and l * l to the slot's record mom[s] = {s1, s2} (k_finish_var, frame.hip, turns the
+// records into the plane).  The records arrive in req_count's place, which no step kernel reads
+// (k_shade<MOM>'s route, shade.hip).  Every sample end passes through `finish` — the direct end, the
+// deferred one (fin / rad_fin) and the drain — so that is the one site.  The record is carried in
+// registers for the launch, loaded and stored beside the pixel's sum: every lane of a slot's group
+// carries the same bits and the lead lane stores (XRT_MOM_REGS, tuning.h; 0: a read-modify-write at
+// the site by the lead lane, measured 2-5 % slower).  The records are zeroed before
+// seeding (render_impl): k_camlist's retired pixels never reach this kernel.  The MOM builds are a
+// unit of their own (XRT_STEP_MOM_UNIT, the file's header).
+template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, bool GROUPED, bool MOM = false>
 __device__ __forceinline__ void step_merged_body(
     const KParams* __restrict__ Pp, const StepObjs SO,   // by value as the kernels take it (by reference: 4 spilled VGPRs in the group kernel for 2)
     const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
-    uint32_t* req_count, uint32_t visits, uint32_t grp) {
+    std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits, uint32_t grp) {
     constexpr int NW = 6 + 2 * NL;   // most words one segment draws (see the header)
     static_assert(!GROUPED || (SPW == 64 && G == 1 && !LANE && !BVH), "groups: whole waves of one-level scenes");
     WaveClock wclk(GROUPED ? grp : ~0u);   // experiment builds (XRT_PHASE_CLOCK): the wave's entry and exit clocks
@@ -588,6 +607,7 @@ __device__ __forceinline__ void step_merged_body(
         for (int l = 0; l <= NL; ++l) so[l] = sd[l] = c1[l] = c0[l] = mk(0, 0, 0), stm[l] = 0.0f;
         uint32_t shm = 0;          // shadow rays in flight (bit per light)
         bool ext = false, fin = false;
+        float2 msum = make_float2(0.0f, 0.0f);   // MOM with XRT_MOM_REGS: the slot's record, carried like acc
         const SlotPixel pix = slot_pixel(P, s);
         const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)width * row);
@@ -605,6 +625,7 @@ __device__ __forceinline__ void step_merged_body(
             }
             gf32* pxg = glb<gf32>(px);
             acc = mk(pxg[0], pxg[1], pxg[2]);
+            if constexpr (MOM && XRT_MOM_REGS) msum = req_count[s];
             rng.load(ring);
         }
         uint32_t nseg = 0, nsh = 0, nrej = 0;
@@ -617,6 +638,16 @@ __device__ __forceinline__ void step_merged_body(
                 ++nrej;
             } else {
                 acc = acc + r;
+                if constexpr (MOM) {   // s1 = s1 + l, s2 = s2 + l * l (include/xrt.h, xrt_render_var)
+                    const float l = luminance(r);
+                    if constexpr (XRT_MOM_REGS) {   // every lane of a group carries the same bits
+                        msum.x = msum.x + l, msum.y = msum.y + l * l;
+                    } else if (lead) {
+                        float2 m = req_count[s];
+                        m.x = m.x + l, m.y = m.y + l * l;
+                        req_count[s] = m;
+                    }
+                }
             }
             ++k;
             if (k >= spp) st = ST_DONE;
@@ -818,6 +849,7 @@ __device__ __forceinline__ void step_merged_body(
         bool want_req = false;
         if (live && lead) {
             px[0] = acc.x, px[1] = acc.y, px[2] = acc.z;
+            if constexpr (MOM && XRT_MOM_REGS) req_count[s] = msum;
             want_req = !(st & ST_DONE) && g - rng.c < P.rng_keep;
             P.state[s] = st;
             if (!(st & (ST_DONE | ST_REGEN))) {
@@ -841,25 +873,26 @@ __device__ __forceinline__ void step_merged_body(
 
 // WV (two-level scenes): a register budget for WV waves per SIMD instead of XRT_BVH_WAVES, for
 // launches with too few live slots to fill more (fewer spills)
-template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, int WV = 0>
+template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, int WV = 0, bool MOM = false>
 __global__ __launch_bounds__(kBlock, WV ? WV : (BVH ? XRT_BVH_WAVES : XRT_STEP_WAVES)) void k_step_merged(
     const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
-    uint32_t* req_count, uint32_t visits) {
-    step_merged_body<INTEG, NL, SPW, G, LANE, BVH, false>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, 0u);
+    std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits) {
+    step_merged_body<INTEG, NL, SPW, G, LANE, BVH, false, MOM>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, 0u);
 }
 
 // The same kernel for one partition group of a round (whole waves of a one-level scene): the group
 // as one trailing argument.  A kernel of its own, so that a launch of every partition stays the
 // kernel it was, argument list included.
-template <int INTEG, int NL>
+template <int INTEG, int NL, bool MOM = false>
 __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_merged_group(
     const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, uint32_t* __restrict__ out, uint32_t* out_count, uint32_t* zero_count,
-    uint32_t* req_count, uint32_t visits, uint32_t grp) {
-    step_merged_body<INTEG, NL, 64, 1, false, false, true>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, grp);
+    std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits, uint32_t grp) {
+    step_merged_body<INTEG, NL, 64, 1, false, false, true, MOM>(Pp, SO, list, count, out, out_count, zero_count, req_count, visits, grp);
 }
 
+#ifndef XRT_STEP_MOM_UNIT
 // CLEAR: also clear the slot's ST_RNGREQ (the wavefront / k_step schedules, whose kernels
 // test the flag; the merged kernel clears it itself when it next loads the slot).
 template <bool CLEAR>
@@ -943,11 +976,12 @@ size_t step_merged_lds_bytes(const KParams& P) {
     if (P.two_level) return bvh_step_layout(P, (uint32_t)w).total;
     return merged_wave_off(P, step_layout(P)) + (kBlock / 64) * w;
 }
+#endif   // !XRT_STEP_MOM_UNIT
 
-template <int INTEG, int SPW, int G, bool LANE, bool BVH = false, int WV = 0>
+template <bool MOM, int INTEG, int SPW, int G, bool LANE, bool BVH = false, int WV = 0>
 static void launch_merged_i(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                             const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
-                            uint32_t* req_count, uint32_t visits, uint32_t part_live, size_t lds, uint32_t grp,
+                            std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits, uint32_t part_live, size_t lds, uint32_t grp,
                             hipStream_t st) {
     // one block per per_block live entries of the fullest partition (part_iter strides over
     // any remainder, so an upper bound on the live count is all the grid needs), for each of
@@ -959,18 +993,19 @@ static void launch_merged_i(const KParams& P, const KParams* dP, const StepObjs&
         // one of several groups (launch_step_merged has checked that the layout is the whole-wave one)
         if constexpr (SPW == 64 && G == 1 && !LANE && !BVH) {
             if (((grp >> 4) & 15u) > 1u) {
-                hipLaunchKernelGGL((k_step_merged_group<INTEG, NL>), dim3(blocks), dim3(kBlock), lds, st, dP, SO, list, count,
+                hipLaunchKernelGGL((k_step_merged_group<INTEG, NL, MOM>), dim3(blocks), dim3(kBlock), lds, st, dP, SO, list, count,
                                    out, out_count, zero, req_count, visits, grp);
                 return;
             }
         }
-        hipLaunchKernelGGL((k_step_merged<INTEG, NL, SPW, G, LANE, BVH, WV>), dim3(blocks), dim3(kBlock), lds, st, dP, SO,
+        hipLaunchKernelGGL((k_step_merged<INTEG, NL, SPW, G, LANE, BVH, WV, MOM>), dim3(blocks), dim3(kBlock), lds, st, dP, SO,
                            list, count, out, out_count, zero, req_count, visits);
     };
     if constexpr (BVH) with_const<1, 2>(P.n_lights, go);   // use_step_bvh: 1 or 2 lights
     else with_const<0, 1, 2, 3, 4>(P.n_lights, go);
 }
 
+#ifndef XRT_STEP_MOM_UNIT
 // slots per wave for a shard of `live` slots
 // (xrt_render_params.slots_per_wave overrides it; results do not depend on it)
 uint32_t step_merged_spw(const KParams& P, uint64_t live) {
@@ -998,17 +1033,20 @@ uint32_t step_merged_group(const KParams& P, uint32_t spw) {
     const bool group = P.n_tris <= 64 && !(P.rflags & XRT_FLAG_NO_GROUP);   // group trace: 64-bit triangle masks
     return spw < 64 && group ? 64u / spw : 1u;
 }
+#endif   // !XRT_STEP_MOM_UNIT
 
-template <int INTEG>
+// MOM: the moments builds, the records in req_count's place; they leave out the XRT_LANE_TRACE experiment layout
+template <bool MOM, int INTEG>
 static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
-                              uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t part_live, size_t lds,
+                              std::conditional_t<MOM, float2*, uint32_t*> req_count, uint32_t visits, uint64_t live, uint32_t part_live, size_t lds,
                               uint32_t grp, hipStream_t st) {
     const bool group = P.n_tris <= 64 && !(P.rflags & XRT_FLAG_NO_GROUP);   // group trace: 64-bit triangle masks
     const bool lane64 = group && exp_env("XRT_LANE_TRACE");   // experiment: per-lane traces, full waves
+    (void)lane64;
     if (P.two_level) {   // use_step_bvh (never group traces: n_tris > 64)
 #define XRT_BVH_CASE(SPWV) \
-    launch_merged_i<INTEG, SPWV, 1, false, true>(P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, \
+    launch_merged_i<MOM, INTEG, SPWV, 1, false, true>(P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, \
                                                  part_live, lds, grp, st)
         switch (step_merged_spw(P, live)) {
             case 64: XRT_BVH_CASE(64); break;
@@ -1017,7 +1055,7 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
                 // below XRT_BVH_LOW_LIVE live slots (a frame's or a row shard's tail) the
                 // XRT_BVH_LOW_WAVES build: more registers per wave, fewer spills
                 if (live < XRT_BVH_LOW_LIVE)
-                    launch_merged_i<INTEG, 16, 1, false, true, XRT_BVH_LOW_WAVES>(
+                    launch_merged_i<MOM, INTEG, 16, 1, false, true, XRT_BVH_LOW_WAVES>(
                         P, dP, *P.sstep, list, count, out, out_count, zero, req_count, visits, part_live, lds, grp, st);
                 else
                     XRT_BVH_CASE(16);
@@ -1027,9 +1065,17 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
         return;
     }
 #define XRT_MERGED_CASE(SPWV, GV, LV) \
-    launch_merged_i<INTEG, SPWV, GV, LV>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, part_live, lds, grp, st)
+    launch_merged_i<MOM, INTEG, SPWV, GV, LV>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, part_live, lds, grp, st)
     switch (step_merged_spw(P, live)) {
-        case 64: if (lane64) XRT_MERGED_CASE(64, 1, true); else XRT_MERGED_CASE(64, 1, false); break;
+        case 64:
+            if constexpr (!MOM) {
+                if (lane64) {
+                    XRT_MERGED_CASE(64, 1, true);
+                    break;
+                }
+            }
+            XRT_MERGED_CASE(64, 1, false);
+            break;
         case 32: if (group) XRT_MERGED_CASE(32, 2, true); else XRT_MERGED_CASE(32, 1, false); break;
         case 4: XRT_MERGED_CASE(4, 16, true); break;   // only with group traces (step_merged_spw)
         case 8: XRT_MERGED_CASE(8, 8, true); break;    // only with group traces (step_merged_spw)
@@ -1038,17 +1084,27 @@ static void launch_merged_spw(const KParams& P, const KParams* dP, const StepObj
 #undef XRT_MERGED_CASE
 }
 
+#ifdef XRT_STEP_MOM_UNIT
+constexpr bool kMomUnit = true;
+hipError_t launch_step_merged_mom(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
+                                  const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
+                                  float2* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
+                                  uint32_t groups, uint32_t group, hipStream_t st) {
+    if (!req_count) return hipErrorInvalidValue;   // the slots' {s1, s2} records
+#else
+constexpr bool kMomUnit = false;
 hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
                               uint32_t groups, uint32_t group, hipStream_t st) {
+#endif
     if (group >= groups || !step_groups_eligible(P.n_part, groups)) return hipErrorInvalidValue;
     // groups exist for whole waves of one-level scenes traced by pair passes (k_step_merged_group)
     if (groups > 1 && (P.two_level || step_merged_spw(P, live) != 64 || exp_env("XRT_LANE_TRACE"))) return hipErrorInvalidValue;
     const uint32_t grp = step_group_arg(P.n_part, groups, group);
     const size_t lds = step_merged_lds_bytes(P);
     with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {   // use_step_merged / _bvh
-        launch_merged_spw<decltype(integ)::value>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, live,
+        launch_merged_spw<kMomUnit, decltype(integ)::value>(P, dP, SO, list, count, out, out_count, zero, req_count, visits, live,
                                                   live_part_max, lds, grp, st);
     });
     return hipGetLastError();

@@ -70,7 +70,8 @@ class HipRenderer:
 
     def params(self, scene, width, height, shard_index=0, shard_count=1, timing=False, integrator=None,
                max_depth=None, schedule="auto", slots_per_wave=0, visits_per_launch=0, group=True,
-               accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True, interleave=None):
+               accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True, interleave=None,
+               fused_var=False):
         """schedule: "auto" (fused k_step when the scene fits in LDS — for small triangle
         scenes with merged shadow + extension traces, for Direct / Normal pixel-parallel
         sample chains (k_pixel) — else the multi-pass wavefront), "step" (the per-slot fused
@@ -90,7 +91,9 @@ class HipRenderer:
         XRT_FLAG_NO_OVERLAP: one launch per round); results never depend on it.  interleave: pixels
         interleaved across the merged schedule's path slots (None: the library's rule, large one-level
         renders; True sets XRT_FLAG_INTERLEAVE, any merged render; False sets XRT_FLAG_NO_INTERLEAVE);
-        results never depend on it."""
+        results never depend on it.  fused_var: a variance render (render_var) keeps the schedule
+        render() would take with spec=False and without pixel-parallel chains, instead of the
+        wavefront (XRT_FLAG_VAR_FUSED); same frame and plane; no effect on any other call."""
         if schedule not in ("auto", "step", "wavefront", "step_tri"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if deep not in ("auto", "single", "quad"):
@@ -106,6 +109,7 @@ class HipRenderer:
                    (abi.XRT_FLAG_ACCUMULATE if accumulate else 0) | (0 if spec else abi.XRT_FLAG_NO_SPEC) |
                    (abi.XRT_FLAG_WHITTED_BVH if whitted_bvh else 0) | (0 if overlap else abi.XRT_FLAG_NO_OVERLAP) |
                    (0 if interleave is None else abi.XRT_FLAG_INTERLEAVE if interleave else abi.XRT_FLAG_NO_INTERLEAVE) |
+                   (abi.XRT_FLAG_VAR_FUSED if fused_var else 0) |
                    {"auto": 0, "single": abi.XRT_FLAG_DEEP_SINGLE, "quad": abi.XRT_FLAG_DEEP_QUAD}[deep])
         p.slots_per_wave, p.visits_per_launch = slots_per_wave, visits_per_launch
         return p
@@ -128,8 +132,10 @@ class HipRenderer:
         """The frame and the variance of each pixel's mean luminance (xrt_render_var): ((H, W, 3),
         (H, W)) float32.  The frame is render()'s, bit for bit; the variance plane is what
         denoise_var takes as `variance`.  self.spp must be at least 2.  The path integrators run
-        the wavefront schedule whatever the schedule keywords say; accumulate is refused.  kw:
-        params()'s."""
+        the wavefront schedule whatever the schedule keywords say, unless fused_var=True: then
+        they run the fused or merged schedule render() would choose with spec=False and
+        schedule="step" (or "step_tri") and the other schedule keywords count; the frame and the
+        plane are the same bits either way.  accumulate is refused.  kw: params()'s."""
         if self._uploaded is not scene:
             self.upload(scene)
         p = self.params(scene, width, height, **kw)
@@ -144,8 +150,8 @@ class HipRenderer:
     def render_var_device(self, scene: SceneBundle, width: int, height: int, out_ptr: int, var_ptr: int,
                           after_stream=None, **kw):
         """render_var into device buffers (xrt_render_var_device): out_ptr H*W*3 float32, var_ptr
-        H*W float32 (torch tensor .data_ptr()).  after_stream as for render_aov_device.  Returns
-        the stats when both planes are complete."""
+        H*W float32 (torch tensor .data_ptr()).  after_stream as for render_aov_device.  fused_var
+        as for render_var.  Returns the stats when both planes are complete."""
         if self._uploaded is not scene:
             self.upload(scene)
         p = self.params(scene, width, height, **kw)
