@@ -193,6 +193,17 @@ enum {
     XRT_FLAG_VAR_FUSED = 8192u, /* xrt_render_var / xrt_render_var_device only: the path integrators
                                    keep the fused or merged schedule instead of the wavefront (see
                                    there); every other entry point ignores it; same results      */
+    XRT_FLAG_CHUNKS = 16384u,   /* merged schedule, one-level scenes: while whole waves run, the live
+                                   slots stay in chunks of 256 that one block per launch owns and
+                                   steps for several rounds (k_step_merged_chunks, csrc/step_chunks.h)
+                                   instead of one launch per round and partition group.  By default
+                                   a large interleaved render of many samples does, when the caller
+                                   sets neither visits_per_launch nor slots_per_wave; this flag makes
+                                   every such render that starts at 64 slots per wave do it.
+                                   XRT_FLAG_NO_OVERLAP keeps its meaning (the grouped rounds before
+                                   and after the phase) and does not disable chunks; same results */
+    XRT_FLAG_NO_CHUNKS = 32768u, /* ... and this one keeps every render on the grouped schedule; it
+                                   wins over XRT_FLAG_CHUNKS                                      */
     XRT_FLAG_ACCUMULATE = 16u  /* Renderer::render's in-place contract (Src/renderer.cpp:75,98):
                                   each owned pixel starts from the value already in the output
                                   buffer (Image::addPixel adds to it in sample order), then
@@ -659,6 +670,12 @@ int xrt_test_camlist(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
  * xrt_test_camlist above is not affected by the map: its lists are always built under the
  * row-major one, slot s = pixel s, whatever p's flags say. */
 int xrt_test_slot_map(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
+/* The chunk phase the render of p would run (csrc/step_chunks.h), a device self-test: plan[0] = 1 if
+ * it keeps its whole-wave phase in chunks, else 0 and nothing else is done; plan[1] = passes per block
+ * per launch; then, after seeding and building the chunks as the render does, plan[2] = the chunks
+ * that hold a slot, plan[3] = the blocks of a launch, and sizes[c] = live slots of chunk c for
+ * c < min(n_sizes, plan[4]), plan[4] = the chunks the buffers hold (numbered 8 j + class). */
+int xrt_test_chunk_plan(xrt_ctx* ctx, const xrt_render_params* p, uint32_t plan[5], uint32_t* sizes, uint32_t n_sizes);
 
 #ifdef __cplusplus
 }

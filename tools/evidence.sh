@@ -14,8 +14,8 @@ rows = list(csv.DictReader(open(glob.glob(sys.argv[1] + "/*kernel_stats.csv")[0]
 top = max(rows, key=lambda r: float(r["TotalDurationNs"]))
 import re
 k = re.search(r"(k_\w+)", top["Name"]).group(1)
-# the merged schedule's step launches (xrt_stats' XRT_K_STEP family) include the group and the speculative kernels
-print("k_step_merged|k_step_spec" if k in ("k_step_merged", "k_step_merged_group") else k)
+# the merged schedule's step launches (xrt_stats' XRT_K_STEP family) include the group, the chunk and the speculative kernels
+print("k_step_merged|k_step_spec" if k in ("k_step_merged", "k_step_merged_group", "k_step_merged_chunks") else k)
 PY
 )
 python3 "$R/tools/prof_summary.py" "$R/gpurun_out/$TAG" "$KPAT" --traffic "$CFG" "$R/profiles/traffic_$CFG.json" \

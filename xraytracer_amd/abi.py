@@ -38,6 +38,7 @@ XRT_FLAG_NO_SPEC = 256
 XRT_FLAG_WHITTED_BVH = 512
 XRT_FLAG_NO_OVERLAP = 1024
 XRT_FLAG_INTERLEAVE, XRT_FLAG_NO_INTERLEAVE = 2048, 4096
+XRT_FLAG_CHUNKS, XRT_FLAG_NO_CHUNKS = 16384, 32768
 XRT_FLAG_VAR_FUSED = 8192
 XRT_SCHED_WAVEFRONT, XRT_SCHED_STEP, XRT_SCHED_STEP_TRI, XRT_SCHED_STEP_MERGED, XRT_SCHED_STEP_BVH = 0, 1, 2, 3, 4
 XRT_SCHED_PIXEL, XRT_SCHED_WHITTED, XRT_SCHED_WHITTED_BVH = 5, 6, 7
@@ -228,6 +229,7 @@ SIGNATURES = {
     "xrt_test_fastdiv": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_uint64), u32p]),
     "xrt_test_camlist": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
     "xrt_test_slot_map": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
+    "xrt_test_chunk_plan": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p, u32p, C.c_uint32]),
 }
 
 _lib = None

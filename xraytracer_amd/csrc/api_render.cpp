@@ -236,6 +236,10 @@ struct RenderPlan {
     uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
     uint64_t poll_every, ahead;                    // LivePoll cadence
     uint64_t cap_iters;                            // loop iterations at most
+    // the whole-wave phase in block-owned chunks (step_chunks.h): passes per block per launch (0: the
+    // grouped schedule from the first round on) and the chunks per class its buffers hold
+    uint32_t chunk_passes, chunk_class_cap;
+    bool chunk_forced;   // by XRT_FLAG_CHUNKS: the phase runs however many chunks the build leaves (build_chunks)
     // a variance render (xrt_render_var): the slots' {s1, s2} records, which select the moments
     // builds of k_shade / k_whitted / k_whitted_bvh and, under XRT_FLAG_VAR_FUSED, of k_step /
     // k_step_tri / k_step_merged; null for a plain render
@@ -314,6 +318,26 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom
                     : R.merged                      ? std::min<uint32_t>(kMergedVisits, (kMT - draws) / draws)
                     : (R.volumetric && kVptEvents) ? kVptEventVisits
                                                     : kStepVisits;
+    // the whole-wave phase in block-owned chunks (host/step_chunks.cpp has the rule): one-level
+    // renders traced by pair passes that start in whole waves and are interleaved by the rule above,
+    // with launch geometry left to the library and samples enough for two passes per launch; the flags
+    // force it for any such render that starts in whole waves, or forbid it
+    {
+        ChunkRule cr{};
+        cr.one_level_merged = R.merged && !R.two_level && !R.pixel && !R.whitted && !R.mom && !exp_env("XRT_LANE_TRACE") &&
+                              R.step_visits >= 1 && R.step_visits <= 255;
+        cr.starts_whole_waves = cr.one_level_merged && step_merged_spw(P, n) == 64;
+        cr.interleaved = can_interleave && auto_interleave && R.slot_mul != 0;
+        cr.force = (p->flags & XRT_FLAG_CHUNKS) != 0, cr.forbid = (p->flags & XRT_FLAG_NO_CHUNKS) != 0;
+        cr.visits_req = ev ? 1u : p->visits_per_launch, cr.spw_req = p->slots_per_wave;
+        cr.spp = p->spp, cr.max_depth = p->max_depth, cr.visits = R.step_visits;
+        cr.class_cap = chunk_class_cap(R.n_part, R.part_cap);
+        const char* eq = exp_env("XRT_CHUNK_Q");   // experiment builds only
+        cr.pass_cap = eq ? (uint32_t)std::min(255, std::max(1, std::atoi(eq))) : XRT_CHUNK_PASSES;
+        R.chunk_passes = chunk_plan(cr);
+        R.chunk_class_cap = cr.class_cap;
+        R.chunk_forced = cr.force;
+    }
     // k_step_spec reads up to kSpecDraws words past the cursor per visit: fewer visits per launch
     // (with XRT_SPEC_TWIST it twists in-loop instead: XRT_SPEC_VISITS visits unless the caller sets them)
     R.spec_visits = !R.spec          ? 0
@@ -356,7 +380,8 @@ struct LivePoll {
     uint64_t live_hint;       // live slots at the last retired poll
     uint32_t live_part_max;   // ... in the fullest partition
     bool done = false;
-    struct Pending { uint64_t it; int slot; uint32_t groups; };
+    uint64_t retired = 0;     // polls retired so far
+    struct Pending { uint64_t it; int slot; uint32_t groups; bool parts; };   // parts: the counters are per partition (part_max when issued)
     std::vector<Pending> pending;
     int issued = 0;
 
@@ -371,7 +396,7 @@ struct LivePoll {
                                          hipMemcpyDeviceToHost, st));
                 HIPCHK(c, hipEventRecord(c->poll_ev[ps][g], st));
             }
-            pending.push_back({it, ps, groups});
+            pending.push_back({it, ps, groups, part_max});
         }
         while (!pending.empty()) {
             const Pending q = pending.front();
@@ -388,10 +413,11 @@ struct LivePoll {
                 const uint32_t v = h0[step_group_of(q.groups, k) * kMaxParts + k];
                 alive += v, pmax = std::max(pmax, v);
             }
+            ++retired;
             if (alive == 0) done = true;
             if (alive < live_hint) {
                 live_hint = alive;
-                if (part_max) live_part_max = std::max(1u, pmax);
+                if (part_max && q.parts) live_part_max = std::max(1u, pmax);
             }
             pending.erase(pending.begin());
             if (done) break;
@@ -484,14 +510,77 @@ class StepGroupStreams {
     bool forked_ = false;
 };
 
-int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, LivePoll& poll,
-              uint64_t& it) {
+// The chunk buffer of a render whose plan has the chunk phase (launch.h ChunkBufs), and the chunks
+// themselves from the seeded lists: timed with the seeding.  The host then reads the header back (one
+// wait for the seeding per frame): the chunks that hold a slot, and the grid of the phase's launches
+// from them, 8 blocks per chunk of the fullest class, at most 8 * kChunkClassBlocks.  A phase taken by
+// the rule, not forced, runs only where no block owns more than one chunk (at most kChunkClassBlocks
+// chunks per class), which is what has been measured; otherwise B.blocks = 0 and the
+// grouped schedule runs from the seeded lists, which the build has not touched.
+int build_chunks(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, ChunkBufs& B) {
+    const size_t chunks = 8u * (size_t)R.chunk_class_cap, head = kChunkHdrWords + kMaxParts + 2 * chunks;
+    const int rc = ensure(c, c->chunks, (head + 2 * chunks * kChunkSlots) * sizeof(uint32_t));
+    if (rc) return rc;
+    B.hdr = as<uint32_t>(c->chunks), B.part_live = B.hdr + kChunkHdrWords, B.cnt = B.part_live + kMaxParts;
+    B.seg = B.hdr + head, B.class_cap = R.chunk_class_cap;
+    HIPCHK(c, hipMemsetAsync(B.hdr, 0, head * sizeof(uint32_t), c->stream));
+    HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_chunks_build(P, B, L.list[0], L.counts(0), c->stream); }));
+    uint32_t head_words[kChunkHdrWords];
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(head_words, B.hdr, sizeof(head_words), hipMemcpyDeviceToHost));
+    uint32_t max_nx = 0;
+    B.chunks = 0;
+    for (uint32_t x = 0; x < 8; ++x) B.chunks += head_words[x], max_nx = std::max(max_nx, head_words[x]);
+    B.blocks = 8u * chunk_class_blocks(max_nx);
+    if (!R.chunk_forced && max_nx > kChunkClassBlocks) B.blocks = 0;
+    return XRT_OK;
+}
+
+// The whole-wave phase in block-owned chunks, ahead of run_fused's loop and counted as its first
+// iterations: launch `it` adds the live slots it leaves to counts((it + 1) % 3) and clears
+// counts((it + 2) % 3), the rotation of the loop, so LivePoll reads it as any round (the sums are per
+// block, not per partition: the fullest partition is not followed here).  The host stays one launch
+// ahead of the last retired poll, a launch being several rounds long.  The phase ends when a retired
+// poll finds fewer live slots than whole waves are worth (kMergedLive64), or none; then
+// k_chunks_scatter puts the live slots back on the partition lists, as round `it` expects them.
+int run_chunks(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, const ChunkBufs& B, LaunchTimer& T,
+               LivePoll& poll, uint64_t& it) {
+    const KParams* dP = as<KParams>(c->kparams);
+    const bool part_max = poll.part_max;
+    const uint64_t ahead = poll.ahead;
+    poll.part_max = false, poll.ahead = 1;
+    int rc = XRT_OK;
+    for (it = 0; it < R.cap_iters && !poll.done; ++it) {
+        if (poll.retired && poll.live_hint < kMergedLive64) break;
+        T.step_live.push_back(poll.live_hint);
+        T.S.layout_launches[0]++;
+        const hipError_t e = T.launch(XRT_K_STEP, [&] {
+            return launch_step_merged_chunks(P, dP, c->step_objs, B, L.counts((it + 1) % 3), L.counts((it + 2) % 3),
+                                             R.step_visits, R.chunk_passes, (uint32_t)it, c->stream);
+        });
+        if (e != hipSuccess) return hip_err(c, e, "k_step_merged_chunks");
+        if ((rc = poll.after(it, L.counts((it + 1) % 3)))) break;
+    }
+    poll.part_max = part_max, poll.ahead = ahead;
+    if (rc || poll.done) return rc;
+    HIPCHK(c, hipMemsetAsync(L.counts(it % 3), 0, P.n_part * sizeof(uint32_t), c->stream));
+    HIPCHK(c, T.launch(XRT_K_SEED, [&] { return launch_chunks_scatter(P, B, L.list[it & 1], L.counts(it % 3), c->stream); }));
+    return XRT_OK;
+}
+
+int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, const ChunkBufs& B, LaunchTimer& T,
+              LivePoll& poll, uint64_t& it) {
     const KParams* dP = as<KParams>(c->kparams);
     const uint32_t blocks = P.n_part * ((P.part_cap + 255) / 256);   // k_step, k_step_tri: one entry per thread
     // built before the first launch that reads them (seed_paths has when it elides), timed with the seeding
     bool camlist_pending = R.camlist && !R.elide;
     StepGroupStreams GS(c, T, R.groups);
-    for (it = 0; it < R.cap_iters && !poll.done; ++it) {
+    it = 0;
+    if (R.chunk_passes && B.blocks) {   // the group streams fork after it, if whole waves are still worth running
+        const int rc = run_chunks(c, P, R, L, B, T, poll, it);
+        if (rc) return rc;
+    }
+    for (; it < R.cap_iters && !poll.done; ++it) {
         const uint32_t *list = L.list[it & 1], *ci = L.counts(it % 3);
         uint32_t *out = L.list[~it & 1], *co = L.counts((it + 1) % 3), *cz = L.counts((it + 2) % 3);
         const uint32_t spw = R.merged ? step_merged_spw(P, poll.live_hint) : 0;
@@ -593,7 +682,7 @@ int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
 }  // namespace
 
 int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st, int wait,
-                hipStream_t wait_stream, float* d_var) {
+                hipStream_t wait_stream, float* d_var, ChunkProbe* probe) {
     const auto t_start = std::chrono::steady_clock::now();
     int rc = check_render(c, p);
     if (rc) return rc;
@@ -635,6 +724,10 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     }
     const RenderPlan R = plan_render(P, p, d_var ? as<float2>(c->mom) : nullptr);
     if (!R.pixel && R.rng_keep > kMT) return set_err(c, XRT_ERR_INVALID, "visits_per_launch too large for the RNG ring");
+    if (probe) {
+        probe->passes = R.chunk_passes;
+        if (!R.chunk_passes) return XRT_OK;
+    }
     P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep, P.slot_mul = R.slot_mul;
     const size_t lcap = (size_t)P.n_part * P.part_cap;
     const LiveLists L{{as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap}, as<uint32_t>(c->counts)};
@@ -660,11 +753,21 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     // first visit), and a pixel k_camlist retires is never loaded by one: its record stays {+0, +0}
     if (R.mom && R.fused && !R.pixel) HIPCHK(c, hipMemsetAsync(R.mom, 0, n * sizeof(float2), c->stream));
     if ((rc = seed_paths(c, P, R, L, T))) return rc;
+    ChunkBufs CB{};
+    if (R.chunk_passes && (rc = build_chunks(c, P, R, L, T, CB))) return rc;
+    if (probe) {   // xrt_test_chunk_plan: the chunks as built, nothing rendered
+        const uint32_t cap = 8u * CB.class_cap;
+        std::vector<uint32_t> cnt(2 * (size_t)cap);
+        HIPCHK(c, hipMemcpy(cnt.data(), CB.cnt, cnt.size() * 4, hipMemcpyDeviceToHost));   // build_chunks has waited
+        probe->chunks = CB.chunks, probe->blocks = CB.blocks, probe->cap = cap;   // blocks 0: bounded off, the grouped schedule runs
+        for (uint32_t q = 0; q < cap && q < probe->n_sizes; ++q) probe->sizes[q] = cnt[2 * q] + cnt[2 * q + 1];
+        return XRT_OK;
+    }
 
     // run, finish
     LivePoll poll{c, P.n_part, R.poll_every, R.ahead, R.merged && !P.spw_req, n, P.part_cap};
     uint64_t it = 0;
-    if (!R.pixel && (rc = R.fused ? run_fused(c, P, R, L, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it)))
+    if (!R.pixel && (rc = R.fused ? run_fused(c, P, R, L, CB, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it)))
         return rc;
     HIPCHK(c, T.launch(XRT_K_FINISH, [&] {   // a variance render's plane counts as part of the finish
         const hipError_t e = launch_finish(P, c->stream);
@@ -742,6 +845,21 @@ int xrt_test_slot_map(xrt_ctx* c, const xrt_render_params* p, uint32_t* out) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     free_buf(d);
     return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_slot_map");
+}
+
+// the chunk phase the render of p would run, its chunks built as the render builds them
+int xrt_test_chunk_plan(xrt_ctx* c, const xrt_render_params* p, uint32_t plan[5], uint32_t* sizes, uint32_t n_sizes) {
+    c = first_device(c);
+    if (!c || !p || !plan || (!sizes && n_sizes)) return XRT_ERR_INVALID;
+    ChunkProbe probe{0, 0, 0, 0, sizes, n_sizes};
+    std::memset(plan, 0, 5 * sizeof(uint32_t));
+    if ((size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width == 0) return check_render(c, p);
+    xrt_render_params q = *p;
+    q.flags &= ~(uint32_t)XRT_FLAG_ACCUMULATE;   // the context's own framebuffer, cleared
+    const int rc = render_impl(c, &q, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &probe);
+    if (rc) return rc;
+    plan[0] = probe.passes != 0 && probe.blocks != 0, plan[1] = probe.passes, plan[2] = probe.chunks, plan[3] = probe.blocks, plan[4] = probe.cap;
+    return XRT_OK;
 }
 
 // ---------------------------------------------------------- variance render ----

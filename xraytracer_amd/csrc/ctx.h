@@ -46,6 +46,7 @@ struct xrt_ctx {
     // xrt_render_var: per slot the {s1, s2} luminance moments (float2), and the context's own
     // variance plane (host output, sub-contexts of a multi render)
     xrt::DevBuf mom, var;
+    xrt::DevBuf chunks;   // the merged schedule's chunk phase: header, counters and list segments (step_chunks.h)
     uint32_t* h_poll = nullptr;  // pinned: LivePoll's 8 slots of kMaxParts counts for each of kMaxStepGroups groups
     std::vector<hipEvent_t> events;   // LaunchTimer's pairs
     hipEvent_t poll_ev[8][xrt::kMaxStepGroups] = {};  // LivePoll's events (created once), slot by group
@@ -178,8 +179,15 @@ int grow_slots(xrt_ctx* c, size_t n);
 KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* fb);
 // wait, wait_stream: order_after's.  d_var: a variance render (xrt_render_var) — the device plane
 // [height][width] that gets the variance of each pixel's mean luminance; null: a plain render
+// probe: xrt_test_chunk_plan — the plan's chunk phase and, when it has one, the chunks built after
+// seeding; the call then returns without rendering
+struct ChunkProbe {
+    uint32_t passes, chunks, blocks, cap;   // passes per launch (0: no phase); chunks that hold a slot; blocks of a launch; chunks the buffers hold
+    uint32_t* sizes;                        // live slots of chunk q < min(cap, n_sizes)
+    uint32_t n_sizes;
+};
 int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st, int wait = 0,
-                hipStream_t wait_stream = nullptr, float* d_var = nullptr);
+                hipStream_t wait_stream = nullptr, float* d_var = nullptr, ChunkProbe* probe = nullptr);
 
 // ---- api_multi.cpp: the multi-GPU context
 // its first device, where frames and planes are assembled (a single-device context: itself)

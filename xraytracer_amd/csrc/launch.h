@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "slot_map.h"
+#include "step_chunks.h"
 #include "step_groups.h"
 #include "wavefront.h"
 
@@ -139,6 +140,24 @@ hipError_t launch_step_merged_mom(const KParams& P, const KParams* dP, const Ste
                                   const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                                   float2* mom, uint32_t visits, uint64_t live, uint32_t live_part_max,
                                   uint32_t groups, uint32_t group, hipStream_t st);
+// The whole-wave phase in block-owned chunks (step_chunks.h).  The chunk buffer: header words (chunks
+// and live slots per class), the partitions' live counts without the retired pixels, two counters
+// per chunk and two segments of kChunkSlots entries per chunk, for 8 * class_cap chunks.
+struct ChunkBufs {
+    uint32_t *hdr, *part_live, *cnt, *seg;
+    uint32_t class_cap;
+    uint32_t chunks, blocks;   // after the build: chunks that hold a slot; blocks of a launch of the phase (0: the phase does not run)
+};
+// the chunks from the seeded partition lists (header and counters cleared by the caller before)
+hipError_t launch_chunks_build(const KParams& P, const ChunkBufs& B, const uint32_t* list, const uint32_t* count,
+                               hipStream_t st);
+// one launch of the phase, numbered rot: `passes` passes of `visits` visits per block; adds the live
+// slots left to live_count (n_part words, cleared before) and clears zero, as a step launch does
+hipError_t launch_step_merged_chunks(const KParams& P, const KParams* dP, const StepObjs& SO, const ChunkBufs& B,
+                                     uint32_t* live_count, uint32_t* zero, uint32_t visits, uint32_t passes, uint32_t rot,
+                                     hipStream_t st);
+// the chunks' live slots onto the partition lists `out` (counters out_count, cleared before)
+hipError_t launch_chunks_scatter(const KParams& P, const ChunkBufs& B, uint32_t* out, uint32_t* out_count, hipStream_t st);
 #if XRT_PHASE_CLOCK
 // experiment builds: the merged kernels' per-wave entry / exit clocks of the work queued on st so far,
 // written to `path` (null: dropped) and cleared; tools/wave_timeline.py reads the file

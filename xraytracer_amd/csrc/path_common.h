@@ -8,6 +8,7 @@
 
 #include "device_math.h"
 #include "slot_map.h"
+#include "step_chunks.h"
 #include "step_groups.h"
 #include "wavefront.h"
 #include "xrt.h"
@@ -348,6 +349,96 @@ __device__ __forceinline__ PartIter part_iter(const uint32_t* count, uint32_t pe
 __device__ __forceinline__ void zero_parts(uint32_t* c, uint32_t grp) {
     if (blockIdx.x == 0)
         for (uint32_t i = threadIdx.x; i < (grp >> 8); i += kBlock) c[step_group_part((grp >> 4) & 15u, grp & 15u, i)] = 0;
+}
+
+// The chunk phase of the merged schedule (step_chunks.h): the chunks this block owns in this launch
+// and the passes it has left.  A chunk c has two list segments seg + (2 c + h) * kChunkSlots and two
+// counters cnt[2 c + h], one of them 0: the other names the segment that holds its live slots.  The
+// block keeps its chunks' live counts in an LDS table for the launch (global memory gets every
+// update too: the next launch's owner reads it there), so a pass reads no counter that a pass
+// before it wrote.  Every value here is block-uniform, and said to be so (part_iter above).
+struct ChunkIter {
+    uint32_t *seg, *cnt;
+    uint32_t* tab;        // LDS: per owned chunk live | h << 16, then the waves' survivor counts of a pass
+    uint32_t x, bj, nx, m, rot, T;
+    uint32_t t, left;     // the table entry the next pass starts looking at; passes left
+    uint32_t c, h, n;     // the pass's chunk, its input segment and live slots
+};
+__device__ __forceinline__ uint32_t* chunk_table() {
+    __shared__ uint32_t tab[kChunkOwnMax + kBlock / 64];
+    return tab;
+}
+__device__ __forceinline__ uint32_t chunk_uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+// hdr: k_chunks_build's header (chunks per class).  Ends with a barrier: the table is loaded.
+__device__ __forceinline__ ChunkIter chunk_iter(const uint32_t* hdr, uint32_t* cnt, uint32_t* seg, uint32_t rot,
+                                                uint32_t passes) {
+    ChunkIter K;
+    K.seg = seg, K.cnt = cnt, K.tab = chunk_table();
+    uint32_t max_nx = 0;
+    for (uint32_t x = 0; x < 8u; ++x) max_nx = max(max_nx, hdr[x]);
+    K.x = blockIdx.x & 7u, K.bj = blockIdx.x >> 3;
+    K.nx = chunk_uni(hdr[K.x]);
+    K.m = chunk_uni(min(chunk_class_blocks(max_nx), gridDim.x >> 3));
+    K.rot = rot;
+    K.T = chunk_uni(min(K.nx ? chunk_owned(K.bj, K.nx, K.m) : 0u, kChunkOwnMax));
+    // the block starts each launch at another of its chunks, so with more chunks than passes every chunk gets its turn
+    K.t = K.T ? rot % K.T : 0u, K.left = passes, K.c = K.h = K.n = 0;
+    for (uint32_t t = threadIdx.x; t < K.T; t += kBlock) {
+        const uint32_t c = 8u * chunk_owned_at(K.bj, t, K.nx, K.m, rot) + K.x;
+        const uint32_t n0 = cnt[2u * c], n1 = cnt[2u * c + 1u];
+        K.tab[t] = n0 ? n0 : (n1 | 1u << 16);
+    }
+    __syncthreads();
+    return K;
+}
+// the block's next pass: round robin over its chunks that still have live slots; false: none, or no pass left
+__device__ __forceinline__ bool chunk_next(ChunkIter& K) {
+    if (K.left == 0u) return false;
+    for (uint32_t k = 0; k < K.T; ++k) {
+        uint32_t t = K.t + k;
+        t = t >= K.T ? t - K.T : t;
+        const uint32_t v = chunk_uni(K.tab[t]);
+        if (v & 0xffffu) {
+            K.c = 8u * chunk_uni(chunk_owned_at(K.bj, t, K.nx, K.m, K.rot)) + K.x;
+            K.h = v >> 16, K.n = v & 0xffffu;
+            K.t = t;
+            --K.left;
+            return true;
+        }
+    }
+    return false;
+}
+// The end of a pass: the block's surviving slots into the chunk's other segment, wave after wave in
+// lane order (the waves' counts meet in LDS at a barrier: no atomic), then the chunk's counters and
+// table entry.  Must be called by every thread of the block; chunk_pass_end's barrier follows it.
+__device__ __forceinline__ void chunk_append(ChunkIter& K, bool want, uint32_t v, int lane, int tid) {
+    uint32_t* wcnt = K.tab + kChunkOwnMax;
+    const uint64_t m = __ballot(want);
+    if (lane == 0) wcnt[tid >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) {
+        const uint32_t q = wcnt[w];
+        before += w < (tid >> 6) ? q : 0u;
+        total += q;
+    }
+    uint32_t* out = K.seg + (size_t)(2u * K.c + (K.h ^ 1u)) * kChunkSlots;
+    if (want) out[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
+    if (tid == 0) {
+        K.cnt[2u * K.c + K.h] = 0u;
+        K.cnt[2u * K.c + (K.h ^ 1u)] = total;
+        K.tab[K.t] = total | (K.h ^ 1u) << 16;
+    }
+    K.t = K.t + 1u >= K.T ? 0u : K.t + 1u;
+}
+// what the pass wrote — list, counters, slot state, rings — is visible to the block's next pass
+__device__ __forceinline__ void chunk_pass_end() { __syncthreads(); }
+// the live slots the block's chunks are left with (after the last pass's barrier)
+__device__ __forceinline__ uint32_t chunk_live(const ChunkIter& K) {
+    uint32_t sum = 0;
+    for (uint32_t t = 0; t < K.T; ++t) sum += K.tab[t] & 0xffffu;
+    return sum;
 }
 
 

@@ -492,7 +492,14 @@ struct WaveClock {
 // the site by the lead lane, measured 2-5 % slower).  The records are zeroed before
 // seeding (render_impl): k_camlist's retired pixels never reach this kernel.  The MOM builds are a
 // unit of their own (XRT_STEP_MOM_UNIT, the file's header).
-template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, bool GROUPED, bool MOM = false>
+//
+// CHUNKS: the body of k_step_merged_chunks, the whole-wave phase in block-owned chunks (step_chunks.h,
+// ChunkIter in path_common.h): the outer loop is the block's passes over its own chunks instead of a
+// walk over a partition's list, a pass's survivors go to the chunk's other segment, and the block
+// meets at a barrier between passes.  count: the chunk header, req_count: the chunks' counters, out:
+// their segments, out_count: the launch's live counters, visits: visits | passes << 8, grp: the
+// launch's rotation.  Nothing inside a visit differs.
+template <int INTEG, int NL, int SPW, int G, bool LANE, bool BVH, bool GROUPED, bool MOM = false, bool CHUNKS = false>
 __device__ __forceinline__ void step_merged_body(
     const KParams* __restrict__ Pp, const StepObjs SO,   // by value as the kernels take it (by reference: 4 spilled VGPRs in the group kernel for 2)
     const uint32_t* __restrict__ list,
@@ -502,6 +509,7 @@ __device__ __forceinline__ void step_merged_body(
     static_assert(!GROUPED || (SPW == 64 && G == 1 && !LANE && !BVH), "groups: whole waves of one-level scenes");
     WaveClock wclk(GROUPED ? grp : ~0u);   // experiment builds (XRT_PHASE_CLOCK): the wave's entry and exit clocks
     static_assert(!BVH || (G == 1 && !LANE), "two-level scenes trace by pair passes");
+    static_assert(!CHUNKS || (SPW == 64 && G == 1 && !LANE && !BVH && !GROUPED && !MOM), "chunks: whole waves of one-level scenes");
     const KParams& P = *Pp;
     extern __shared__ __attribute__((aligned(16))) f4 lds_m[];
     char* lb = reinterpret_cast<char*>(lds_m);
@@ -577,13 +585,21 @@ __device__ __forceinline__ void step_merged_body(
     // req_count is not touched here (only the seeding refill reads a request list)
     if constexpr (GROUPED) zero_parts(zero_count, grp);
     else zero_parts(P, zero_count);
-    const PartIter it = GROUPED ? part_iter(count, (kBlock / 64) * SPW, grp) : part_iter(P, count, (kBlock / 64) * SPW);
+    ChunkIter ck;   // CHUNKS only
+    if constexpr (CHUNKS) {
+        ck = chunk_iter(count, req_count, out, grp, visits >> 8);
+        visits &= 255u;
+    }
+    const PartIter it = CHUNKS    ? PartIter{0u, 0u, 0u, 0u}
+                        : GROUPED ? part_iter(count, (kBlock / 64) * SPW, grp)
+                                  : part_iter(P, count, (kBlock / 64) * SPW);
     const uint32_t spp = P.spp, max_depth = P.max_depth, width = P.width;
-    for (uint32_t base = it.first; base < it.n; base += it.stride) {
+    for (uint32_t base = it.first; CHUNKS ? chunk_next(ck) : base < it.n; base += it.stride) {
+        const uint32_t n_in = CHUNKS ? ck.n : it.n;   // entries of the list this pass reads
         const uint32_t i = base + (uint32_t)(tid >> 6) * SPW + (uint32_t)lane / G;
-        const bool own = lane / G < SPW && i < it.n;
+        const bool own = lane / G < SPW && i < n_in;
         const bool lead = own && (lane % G) == 0;   // the lane of a group that writes back
-        const uint32_t s = own ? list[it.p * P.part_cap + i] : 0;
+        const uint32_t s = own ? (CHUNKS ? glb<gu32>(ck.seg + (size_t)(2u * ck.c + ck.h) * kChunkSlots)[i] : list[it.p * P.part_cap + i]) : 0;
         uint32_t st = own ? glb<gu32>(P.state)[s] : ST_DONE;
         st &= ~ST_RNGREQ;   // the refill this slot asked for ran after the previous launch
         const bool live = !(st & ST_DONE);
@@ -865,8 +881,16 @@ __device__ __forceinline__ void step_merged_body(
             if (nsh) P.c_shadow[s] += nsh;
             if (nrej) P.c_rej[s] += nrej;
         }
-        wave_append(live && lead && !(st & ST_DONE), s, out + it.p * P.part_cap, out_count + it.p, lane);
+        if constexpr (CHUNKS) chunk_append(ck, live && lead && !(st & ST_DONE), s, lane, tid);
+        else wave_append(live && lead && !(st & ST_DONE), s, out + it.p * P.part_cap, out_count + it.p, lane);
         wave_refill(P, want_req, s, g, lane, reinterpret_cast<uint32_t*>(&W));
+        if constexpr (CHUNKS) chunk_pass_end();
+    }
+    if constexpr (CHUNKS) {   // what the host polls: the live slots left, summed over the launch's blocks
+        if (tid == 0) {
+            const uint32_t left = chunk_live(ck);
+            if (left) atomicAdd(out_count + blockIdx.x % P.n_part, left);
+        }
     }
     wclk.end();
 }
@@ -893,6 +917,127 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_merged_group(
 }
 
 #ifndef XRT_STEP_MOM_UNIT
+// ------------------------------------------------------------- the chunk phase ----
+// The whole-wave phase in block-owned chunks (step_chunks.h; run_fused, api_render.cpp): at most
+// 8 * kChunkClassBlocks blocks, the wave slots of the GPU at XRT_STEP_WAVES, each running `passes`
+// passes of `visits` visits over the chunks it owns in the launch numbered rot, then adding the live
+// slots it is left with to live_count for the host's poll.  A chunk is read and written by one block
+// per launch, so the barrier between passes orders everything; launches are ordered by the stream.
+template <int INTEG, int NL>
+__global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_merged_chunks(
+    const KParams* __restrict__ Pp, const StepObjs SO, const uint32_t* __restrict__ hdr, uint32_t* cnt, uint32_t* seg,
+    uint32_t* live_count, uint32_t* zero_count, uint32_t visits, uint32_t passes, uint32_t rot) {
+    step_merged_body<INTEG, NL, 64, 1, false, false, false, false, true>(Pp, SO, nullptr, hdr, seg, live_count, zero_count, cnt,
+                                                                          visits | passes << 8, rot);
+}
+
+// The chunks of a render from its partition lists, in two launches of one block per partition.
+// k_chunks_count: the partition's live entries that are not ST_DONE (k_camlist's retired pixels stay
+// on the seeded lists; no chunk holds them).
+__global__ __launch_bounds__(kBlock) void k_chunks_count(KParams P, const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ count, uint32_t* part_live) {
+    __shared__ uint32_t red[kBlock / 64];
+    const uint32_t p = blockIdx.x, n = min(count[p], P.part_cap);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t keep = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += kBlock) keep += (P.state[list[(size_t)p * P.part_cap + i]] & ST_DONE) ? 0u : 1u;
+    for (int off = 32; off > 0; off >>= 1) keep += __shfl_down(keep, off);
+    if (lane == 0) red[wv] = keep;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int w = 0; w < kBlock / 64; ++w) tot += red[w];
+        part_live[p] = tot;
+    }
+}
+// k_chunks_build: class x = p % 8 concatenates those entries of the partitions x, x + 8, ... into one
+// dense array, in list order, cut into chunks c = 8 j + x of kChunkSlots entries (segment 0).  The
+// class's first partition also writes its header words and every counter of its chunks, up to the
+// class_cap chunks the buffers hold.  The host has cleared header and counters: a class without a
+// partition has no chunk.
+__global__ __launch_bounds__(kBlock) void k_chunks_build(KParams P, const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ count,
+                                                         const uint32_t* __restrict__ part_live, uint32_t* hdr, uint32_t* cnt,
+                                                         uint32_t* seg, uint32_t class_cap) {
+    __shared__ uint32_t wc[kBlock / 64];
+    const uint32_t p = blockIdx.x, x = p & 7u, n = min(count[p], P.part_cap);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t run = chunk_dense_offset(part_live, p);
+    for (uint32_t base = 0; base < n; base += kBlock) {
+        const uint32_t i = base + (uint32_t)tid;
+        const uint32_t s = i < n ? list[(size_t)p * P.part_cap + i] : 0u;
+        const bool keep = i < n && !(P.state[s] & ST_DONE);
+        const uint64_t m = __ballot(keep);
+        if (lane == 0) wc[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (int w = 0; w < kBlock / 64; ++w) before += w < wv ? wc[w] : 0u, total += wc[w];
+        const uint32_t pos = run + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t j = pos / kChunkSlots;
+        if (keep && j < class_cap) seg[(size_t)(2u * (8u * j + x)) * kChunkSlots + pos % kChunkSlots] = s;
+        run += total;
+        __syncthreads();
+    }
+    if (p < 8u) {
+        const uint32_t tot = chunk_class_live(part_live, P.n_part, x);
+        if (tid == 0) hdr[x] = min(chunks_for(tot), class_cap), hdr[8u + x] = tot;
+        for (uint32_t j = tid; j < class_cap; j += kBlock) {
+            const uint32_t lo = j * kChunkSlots;
+            cnt[2u * (8u * j + x)] = tot > lo ? min(kChunkSlots, tot - lo) : 0u;
+            cnt[2u * (8u * j + x) + 1u] = 0u;
+        }
+    }
+}
+// k_chunks_scatter ends the phase: every chunk's live slots onto the partition lists the grouped
+// schedule goes on with, slot s on the list of its partition s / part_cap (k_seed's), whose counters
+// the host has cleared.  One block per chunk; a wave appends once per partition its slots come from.
+__global__ __launch_bounds__(kBlock) void k_chunks_scatter(KParams P, const uint32_t* __restrict__ cnt,
+                                                           const uint32_t* __restrict__ seg, uint32_t* out, uint32_t* out_count) {
+    const uint32_t c = blockIdx.x, n0 = cnt[2u * c], n1 = cnt[2u * c + 1u];
+    const uint32_t h = n0 ? 0u : 1u, n = min(n0 | n1, kChunkSlots);
+    const int lane = threadIdx.x & 63;
+    const bool have = threadIdx.x < n;
+    const uint32_t s = have ? seg[(size_t)(2u * c + h) * kChunkSlots + threadIdx.x] : 0u;
+    const uint32_t p = min(s / P.part_cap, P.n_part - 1u);
+    uint64_t todo = __ballot(have);
+    while (todo) {
+        const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)p, __builtin_ctzll(todo));
+        const bool mine = have && p == pl;
+        wave_append(mine, s, out + (size_t)pl * P.part_cap, out_count + pl, lane);
+        todo &= ~__ballot(mine);
+    }
+}
+
+hipError_t launch_chunks_build(const KParams& P, const ChunkBufs& B, const uint32_t* list, const uint32_t* count,
+                               hipStream_t st) {
+    hipLaunchKernelGGL(k_chunks_count, dim3(P.n_part), dim3(kBlock), 0, st, P, list, count, B.part_live);
+    hipLaunchKernelGGL(k_chunks_build, dim3(P.n_part), dim3(kBlock), 0, st, P, list, count, B.part_live, B.hdr, B.cnt, B.seg,
+                       B.class_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_chunks_scatter(const KParams& P, const ChunkBufs& B, uint32_t* out, uint32_t* out_count, hipStream_t st) {
+    hipLaunchKernelGGL(k_chunks_scatter, dim3(8u * B.class_cap), dim3(kBlock), 0, st, P, B.cnt, B.seg, out, out_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_merged_chunks(const KParams& P, const KParams* dP, const StepObjs& SO, const ChunkBufs& B,
+                                     uint32_t* live_count, uint32_t* zero, uint32_t visits, uint32_t passes, uint32_t rot,
+                                     hipStream_t st) {
+    if (P.two_level || visits == 0 || visits > 255u || passes == 0 || passes > 255u || B.blocks == 0 ||
+        B.blocks % 8u || B.blocks > 8u * kChunkClassBlocks)
+        return hipErrorInvalidValue;
+    const uint32_t blocks = B.blocks;   // from the chunks as built: 8 per chunk of the fullest class (build_chunks)
+    const size_t lds = step_merged_lds_bytes(P);
+    with_const<XRT_INTEGRATOR_DIRECT, XRT_INTEGRATOR_GI>(P.integrator, [&](auto integ) {   // use_step_merged
+        with_const<0, 1, 2, 3, 4>(P.n_lights, [&](auto nl) {
+            hipLaunchKernelGGL((k_step_merged_chunks<decltype(integ)::value, decltype(nl)::value>), dim3(blocks), dim3(kBlock),
+                               lds, st, dP, SO, B.hdr, B.cnt, B.seg, live_count, zero, visits, passes, rot);
+        });
+    });
+    return hipGetLastError();
+}
+
 // CLEAR: also clear the slot's ST_RNGREQ (the wavefront / k_step schedules, whose kernels
 // test the flag; the merged kernel clears it itself when it next loads the slot).
 template <bool CLEAR>

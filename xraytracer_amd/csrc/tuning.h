@@ -37,6 +37,9 @@
 #ifndef XRT_STEP_GROUPS
 #define XRT_STEP_GROUPS 2    // k_step_merged's full-wave launches of one-level scenes in this many partition groups, each on a stream of its own (1..3; step_groups.h; C2 66.4 -> 51.5 ms; 3: 83.7 ms; 1: one launch per round, the former sequence, 66.2 ms)
 #endif
+#ifndef XRT_CHUNK_PASSES
+#define XRT_CHUNK_PASSES 4   // the whole-wave phase in block-owned chunks (step_chunks.h): passes per block per launch of k_step_merged_chunks, and the passes a render must have samples for to take the phase by the rule (C2, profiles/r11_c2_bench.json: 0, the phase off, 45.22 ms as the parent's 45.31; 4: 42.75; 8: 43.01; 10: 43.17)
+#endif
 #ifndef XRT_SLOT_INTERLEAVE
 #define XRT_SLOT_INTERLEAVE 1    // merged renders interleave pixels across slots (slot_map.h; C2 51.6 -> 45.6 ms): one-level shards of at least XRT_SLOT_INTERLEAVE_MIN slots, two-level ones that start in whole waves (XRT_BVH_LIVE64); 0: only under XRT_FLAG_INTERLEAVE
 #endif

@@ -71,7 +71,7 @@ class HipRenderer:
     def params(self, scene, width, height, shard_index=0, shard_count=1, timing=False, integrator=None,
                max_depth=None, schedule="auto", slots_per_wave=0, visits_per_launch=0, group=True,
                accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True, interleave=None,
-               fused_var=False):
+               fused_var=False, chunks=None):
         """schedule: "auto" (fused k_step when the scene fits in LDS — for small triangle
         scenes with merged shadow + extension traces, for Direct / Normal pixel-parallel
         sample chains (k_pixel) — else the multi-pass wavefront), "step" (the per-slot fused
@@ -93,7 +93,10 @@ class HipRenderer:
         renders; True sets XRT_FLAG_INTERLEAVE, any merged render; False sets XRT_FLAG_NO_INTERLEAVE);
         results never depend on it.  fused_var: a variance render (render_var) keeps the schedule
         render() would take with spec=False and without pixel-parallel chains, instead of the
-        wavefront (XRT_FLAG_VAR_FUSED); same frame and plane; no effect on any other call."""
+        wavefront (XRT_FLAG_VAR_FUSED); same frame and plane; no effect on any other call.  chunks: the
+        merged schedule's whole-wave phase in block-owned chunks (None: the library's rule, large
+        interleaved renders of many samples; True sets XRT_FLAG_CHUNKS, any one-level merged render that
+        starts at 64 slots per wave; False sets XRT_FLAG_NO_CHUNKS); results never depend on it."""
         if schedule not in ("auto", "step", "wavefront", "step_tri"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if deep not in ("auto", "single", "quad"):
@@ -110,6 +113,7 @@ class HipRenderer:
                    (abi.XRT_FLAG_WHITTED_BVH if whitted_bvh else 0) | (0 if overlap else abi.XRT_FLAG_NO_OVERLAP) |
                    (0 if interleave is None else abi.XRT_FLAG_INTERLEAVE if interleave else abi.XRT_FLAG_NO_INTERLEAVE) |
                    (abi.XRT_FLAG_VAR_FUSED if fused_var else 0) |
+                   (0 if chunks is None else abi.XRT_FLAG_CHUNKS if chunks else abi.XRT_FLAG_NO_CHUNKS) |
                    {"auto": 0, "single": abi.XRT_FLAG_DEEP_SINGLE, "quad": abi.XRT_FLAG_DEEP_QUAD}[deep])
         p.slots_per_wave, p.visits_per_launch = slots_per_wave, visits_per_launch
         return p
@@ -369,6 +373,21 @@ class HipRenderer:
         out = np.zeros(len(range(p.shard_index, height, p.shard_count)) * width, np.uint32)
         self._check(self._lib.xrt_test_slot_map(self.ctx, C.byref(p), abi.u32ptr(out)), "xrt_test_slot_map")
         return out
+
+    def chunk_plan(self, scene: SceneBundle, width: int, height: int, **kw) -> dict:
+        """The chunk phase a render with these arguments (those of params) would run (xrt_test_chunk_plan,
+        a device self-test): {"chunks": bool, "passes", "C", "blocks", "sizes"}; sizes[c] are the live
+        slots of chunk c = 8 j + class after the build, C counts the chunks that hold a slot."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        n = len(range(p.shard_index, height, p.shard_count)) * width
+        sizes = np.zeros(8 * (n // 256 + 2), np.uint32)   # chunks are numbered 8 j + class: one class may hold them all
+        plan = np.zeros(5, np.uint32)
+        self._check(self._lib.xrt_test_chunk_plan(self.ctx, C.byref(p), abi.u32ptr(plan), abi.u32ptr(sizes), len(sizes)),
+                    "xrt_test_chunk_plan")
+        return dict(chunks=bool(plan[0]), passes=int(plan[1]), C=int(plan[2]), blocks=int(plan[3]),
+                    sizes=sizes[:min(len(sizes), int(plan[4]))].copy())
 
     def tonemap(self, width: int, height: int, gamma: float, device_ptr: int = 0) -> np.ndarray:
         """Image::gammaCorrection(gamma) + writePPM's 8-bit quantisation on the GPU, of the
