@@ -314,9 +314,26 @@ int  xrt_device_count(const xrt_ctx* ctx);   /* GPUs a context renders on */
 void xrt_destroy(xrt_ctx* ctx);
 const char* xrt_last_error(const xrt_ctx* ctx);   /* ctx may be NULL (create failure) */
 
+/* Where results are bit-identical to the reference.  The acceleration structures an upload
+ * builds (padded object boxes, the plane cull, the padded boxes of the triangle and sphere
+ * BVHs) only skip primitives the reference's in-order scan would have rejected, as long as
+ * the scene's vertices and the origins of the rays traced — the camera's position — lie
+ * within XRT_EXACT_DIAGONALS scene diagonals of the world origin resp. of the scene; a scene
+ * of triangle meshes only: within XRT_EXACT_DIAGONALS_TRI.  The margins of those boxes are
+ * relative to the scene's size, while the float error of a hit grows with the distance of
+ * the ray origin and of the scene from the world origin: beyond the domain a hit within
+ * float error of an object's silhouette, or whose distance the reference's own arithmetic
+ * no longer resolves, may be reported as a miss or as the hit behind it.  Both numbers lie
+ * two octaves below the first failure measured by tests/test_adversarial_rays.py (DESIGN.md
+ * section 3, "Where the culls are exact"). */
+#define XRT_EXACT_DIAGONALS 1.0f
+#define XRT_EXACT_DIAGONALS_TRI 16.0f
 int  xrt_upload_scene(xrt_ctx* ctx, const xrt_scene_desc* scene);
 /* Camera::camera2world (row-major, row-vector convention, Src/geometry.h:486-498),
- * PinholeCamera::scale = tan(0.5*deg2rad(FOV)) and aspect_ratio (Src/camera.h:37-47) */
+ * PinholeCamera::scale = tan(0.5*deg2rad(FOV)) and aspect_ratio (Src/camera.h:37-47).
+ * The eye (c2w's last row) is the origin of every camera ray: renders are bit-identical to
+ * the reference's while it lies within XRT_EXACT_DIAGONALS (XRT_EXACT_DIAGONALS_TRI) scene
+ * diagonals of the scene, however narrow the field of view (see xrt_upload_scene). */
 int  xrt_set_camera(xrt_ctx* ctx, const float c2w[16], float scale, float aspect);
 int  xrt_set_medium(xrt_ctx* ctx, const xrt_medium_desc* medium);
 /* The delta lights of the scene (Scene::getDeltaLights(), Src/scene.h), in order; n = 0 clears
@@ -574,7 +591,12 @@ enum { XRT_QUERY_INTERSECT = 0, XRT_QUERY_OCCLUDED = 1 };
 /* n rays rays[i] = {ox, oy, oz, dx, dy, dz} against the uploaded scene, on the GPU with the
  * render's own trace kernels: XRT_QUERY_INTERSECT fills out[i] like Scene::intersect on a
  * fresh IntersectInfo; XRT_QUERY_OCCLUDED sets out[i].hit = Scene::occluded(ray, tmax[i])
- * (tmax NULL: FLT_MAX) and leaves the other fields zero.  Blocks until done. */
+ * (tmax NULL: FLT_MAX) and leaves the other fields zero.  Blocks until done.
+ * Directions need not be unit vectors.  The answers are the reference's, bit for bit, for
+ * finite rays whose origins lie within XRT_EXACT_DIAGONALS scene diagonals of the scene
+ * (XRT_EXACT_DIAGONALS_TRI for a scene of triangle meshes only) and a scene as far from the
+ * world origin at the most (see xrt_upload_scene); from further away a hit within float
+ * error of an object's silhouette may be reported as a miss. */
 int  xrt_query(xrt_ctx* ctx, uint32_t n, const float* rays, const float* tmax, int32_t mode, xrt_hit* out);
 
 /* Output stage: Image::gammaCorrection(gamma) then writePPM's 8-bit quantisation
