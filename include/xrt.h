@@ -698,6 +698,26 @@ int xrt_test_slot_map(xrt_ctx* ctx, const xrt_render_params* p, uint32_t* out);
  * that hold a slot, plan[3] = the blocks of a launch, and sizes[c] = live slots of chunk c for
  * c < min(n_sizes, plan[4]), plan[4] = the chunks the buffers hold (numbered 8 j + class). */
 int xrt_test_chunk_plan(xrt_ctx* ctx, const xrt_render_params* p, uint32_t plan[5], uint32_t* sizes, uint32_t n_sizes);
+/* How the volumetric kernels read the context's heterogeneous density grid: the per-cell corner
+ * values (a dense grid whose cells take at most the corner limit, 2 GiB), four rows of the dense
+ * grid itself (a larger one, or one without a cell), or leaf bricks (xrt_set_medium_bricks). */
+enum { XRT_DENSITY_CORNERS = 0, XRT_DENSITY_ROWS = 1, XRT_DENSITY_BRICKS = 2 };
+/* The kernels' own density lookup (HeterogeneousMedium::getDensity, multiplier included) of the
+ * context's current medium at the world points points[3 i ..] = {x, y, z}, one lane per point:
+ * out[i]; *layout = the XRT_DENSITY_* in use.  n = 0 only reports the layout.  XRT_ERR_STATE without
+ * a medium or with a homogeneous one.  Exact where the points' index-space coordinates fit an int. */
+int xrt_test_density(xrt_ctx* ctx, const float* points, uint32_t n, float* out, int32_t* layout);
+/* The corner limit of later xrt_set_medium calls on this context (every device of a multi-device
+ * one): a dense grid builds its corner values when (nx-1)(ny-1)(nz-1) * 32 <= max_bytes, so 0
+ * makes every grid read its rows.  The results of a render never depend on it. */
+int xrt_test_corner_grid_limit(xrt_ctx* ctx, uint64_t max_bytes);
+/* The kernels' own HenyeyGreenstein::sampleDirection (Src/medium.h:37-67) over n items: wi[3 i ..]
+ * for g and wo[3 i ..], and Medium::sampleWavelength (Src/medium.h:102-115): channel[i] and
+ * pmf[3 i ..] for thr[3 i ..] and albedo[3 i ..].  Item i's stream is its own eight raw mt19937
+ * state words words[8 i ..] (the generator's output is their tempering), read from the first. */
+int xrt_test_hg(xrt_ctx* ctx, float g, const float* wo, const uint32_t* words, uint32_t n, float* wi);
+int xrt_test_wavelength(xrt_ctx* ctx, const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
+                        uint32_t* channel, float* pmf);
 
 #ifdef __cplusplus
 }

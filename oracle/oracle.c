@@ -1130,6 +1130,9 @@ uint32_t orc_kat_wavelength(orc_mt* m, const float* thr, const float* albedo, fl
     st3(pmf, pm);
     return c;
 }
+void orc_kat_density(const xrt_medium_desc* medium, const float* points, uint32_t n, float* out) {
+    for (uint32_t i = 0; i < n; ++i) out[i] = medium_density(medium, ld3(points + 3 * (size_t)i));
+}
 void orc_kat_light(orc_mt* m, const xrt_light* l, const float* pos, float* out) {
     v3 wi = mk(0, 0, 0);
     float pdf = 0.0f, tmax = 0.0f;

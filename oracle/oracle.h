@@ -14,6 +14,9 @@
  * primitive.cpp, integrator.h, renderer.cpp, scene.cpp all include spdlog / OpenCV /
  * OpenVDB / tinyobjloader, none of which exist in this image) are restated from the
  * source text with file:line citations and are "parity unpinned" beyond those KATs.
+ * So is the density lookup (orc_kat_density): DensityGrid::getDensity is OpenVDB's BoxSampler,
+ * which no binary here can hold it to; the device's lookup and a numpy restatement
+ * (tests/medium_restatement.py) are held to it point by point instead.
  * See DESIGN.md §Oracle.
  */
 #ifndef XRT_ORACLE_H
@@ -90,6 +93,9 @@ int orc_kat_box(const float* o, const float* d, const float* pmin, const float* 
 float orc_kat_hg(orc_mt* m, float g, const float* wo, float* wi);
 /* Medium::sampleWavelength (medium.h:102-115): 1 draw */
 uint32_t orc_kat_wavelength(orc_mt* m, const float* thr, const float* albedo, float* pmf);
+/* HeterogeneousMedium::getDensity (medium.cpp:24-27) over DensityGrid::getDensity (grid.h:71-77)
+ * at n world points {x, y, z}, for index-space coordinates that fit an int.  Unpinned: see above. */
+void orc_kat_density(const xrt_medium_desc* medium, const float* points, uint32_t n, float* out);
 /* QuadLight::sample (light.cpp:59-68) / TriangleLight::sample (light.cpp:21-30) /
  * SphereLight::sample default branch (light.h:157-197).  out: wi[3], pdf, tmax, L[3] */
 void orc_kat_light(orc_mt* m, const xrt_light* l, const float* pos, float* out);

@@ -73,6 +73,8 @@ def lib():
         l.orc_kat_wavelength.argtypes = [C.POINTER(OrcMT), f32p, f32p, f32p]
         l.orc_kat_wavelength.restype = C.c_uint32
         l.orc_kat_light.argtypes = [C.POINTER(OrcMT), C.POINTER(abi.XrtLight), f32p, f32p]
+        l.orc_kat_density.argtypes = [C.POINTER(abi.XrtMediumDesc), f32p, C.c_uint32, f32p]
+        l.orc_kat_density.restype = None
         l.orc_libm_sincosf.argtypes = [f32p, C.c_uint32, f32p, f32p]
         l.orc_libm_logexpf.argtypes = [f32p, C.c_uint32, f32p, f32p]
         l.orc_libm_powf.argtypes = [f32p, C.c_uint32, C.c_float, f32p]
@@ -151,6 +153,15 @@ def mt(seed) -> OrcMT:
     m = OrcMT()
     lib().orc_mt_seed(C.byref(m), seed)
     return m
+
+
+def density(medium, points):
+    """HeterogeneousMedium::getDensity of a scenes.Medium at world points (n, 3): (n,) float32."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), np.float32)
+    md = medium.desc()
+    lib().orc_kat_density(C.byref(md), fp(p), len(p), fp(out))
+    return out
 
 
 def libm_logexpf(x):

@@ -165,6 +165,8 @@ class XrtHit(C.Structure):
 
 
 XRT_QUERY_INTERSECT, XRT_QUERY_OCCLUDED = 0, 1
+XRT_DENSITY_CORNERS, XRT_DENSITY_ROWS, XRT_DENSITY_BRICKS = 0, 1, 2   # xrt_test_density's layout
+DENSITY_LAYOUTS = ("corners", "rows", "bricks")
 
 
 # Every symbol include/xrt.h declares, with its ctypes signature.
@@ -230,6 +232,10 @@ SIGNATURES = {
     "xrt_test_camlist": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
     "xrt_test_slot_map": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p]),
     "xrt_test_chunk_plan": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), u32p, u32p, C.c_uint32]),
+    "xrt_test_density": (C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p, C.POINTER(C.c_int32)]),
+    "xrt_test_corner_grid_limit": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "xrt_test_hg": (C.c_int, [C.c_void_p, C.c_float, f32p, u32p, C.c_uint32, f32p]),
+    "xrt_test_wavelength": (C.c_int, [C.c_void_p, f32p, f32p, u32p, C.c_uint32, u32p, f32p]),
 }
 
 _lib = None

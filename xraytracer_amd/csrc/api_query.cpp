@@ -183,6 +183,80 @@ int xrt_test_trig_draw_domain(xrt_ctx* c, uint32_t first, uint32_t count, float*
     return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_trig_draw_domain");
 }
 
+// the kernels' own medium_density (medium.h) on the context's heterogeneous medium
+int xrt_test_density(xrt_ctx* c, const float* points, uint32_t n, float* out, int32_t* layout) {
+    c = first_device(c);
+    if (!c || !points || !out || !layout) return XRT_ERR_INVALID;
+    const DMedium& M = c->base.medium;
+    if (!c->has_medium || M.kind != XRT_MEDIUM_HETEROGENEOUS)
+        return set_err(c, XRT_ERR_STATE, "xrt_test_density: set a heterogeneous medium first");
+    *layout = M.brick_table ? XRT_DENSITY_BRICKS : M.corners ? XRT_DENSITY_CORNERS : XRT_DENSITY_ROWS;
+    if (n == 0) return XRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf dp, dout;
+    int rc;
+    if ((rc = ensure(c, dp, (size_t)n * 12 + 16)) || (rc = ensure(c, dout, (size_t)n * 4 + 16))) {
+        free_buf(dp), free_buf(dout);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(dp.p, points, (size_t)n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_test_density(M, as<float>(dp), n, as<float>(dout), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+    free_buf(dp), free_buf(dout);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_density");
+}
+
+// the kernels' own hg_sample (medium.h), each item's two draws from its own eight raw words
+int xrt_test_hg(xrt_ctx* c, float g, const float* wo, const uint32_t* words, uint32_t n, float* wi) {
+    c = first_device(c);
+    if (!c || !wo || !words || !wi) return XRT_ERR_INVALID;
+    if (n == 0) return XRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf dwo, dw, dwi;
+    int rc;
+    if ((rc = ensure(c, dwo, (size_t)n * 12 + 16)) || (rc = ensure(c, dw, (size_t)n * 32)) ||
+        (rc = ensure(c, dwi, (size_t)n * 12 + 16))) {
+        free_buf(dwo), free_buf(dw), free_buf(dwi);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(dwo.p, wo, (size_t)n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dw.p, words, (size_t)n * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_test_hg(g, as<float>(dwo), as<uint32_t>(dw), n, as<float>(dwi), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(wi, dwi.p, (size_t)n * 12, hipMemcpyDeviceToHost);
+    free_buf(dwo), free_buf(dw), free_buf(dwi);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_hg");
+}
+
+// the kernels' own sample_wavelength (medium.h), each item's draw from its own eight raw words
+int xrt_test_wavelength(xrt_ctx* c, const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
+                        uint32_t* channel, float* pmf) {
+    c = first_device(c);
+    if (!c || !thr || !albedo || !words || !channel || !pmf) return XRT_ERR_INVALID;
+    if (n == 0) return XRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf dt, da, dw, dc, dp;
+    int rc;
+    if ((rc = ensure(c, dt, (size_t)n * 12 + 16)) || (rc = ensure(c, da, (size_t)n * 12 + 16)) ||
+        (rc = ensure(c, dw, (size_t)n * 32)) || (rc = ensure(c, dc, (size_t)n * 4 + 16)) ||
+        (rc = ensure(c, dp, (size_t)n * 12 + 16))) {
+        free_buf(dt), free_buf(da), free_buf(dw), free_buf(dc), free_buf(dp);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(dt.p, thr, (size_t)n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(da.p, albedo, (size_t)n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dw.p, words, (size_t)n * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = launch_test_wavelength(as<float>(dt), as<float>(da), as<uint32_t>(dw), n, as<uint32_t>(dc), as<float>(dp),
+                                   c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(channel, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(pmf, dp.p, (size_t)n * 12, hipMemcpyDeviceToHost);
+    free_buf(dt), free_buf(da), free_buf(dw), free_buf(dc), free_buf(dp);
+    return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_wavelength");
+}
+
 }  // extern "C"
 
 // every 32-bit input: mode 0 rcp_rn vs 1/b, mode 1 div_const(x, c, rc) vs x / c (device_math.h)

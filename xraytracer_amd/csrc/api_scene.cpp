@@ -521,12 +521,13 @@ int set_medium_one(xrt_ctx* c, const xrt_medium_desc* m) {
     DMedium& D = c->base.medium;
     D = DMedium{};
     D.density = as<float>(c->density);
-    // the per-cell corner layout (8x the grid's bytes; skipped above 2 GiB).  It is only an
+    // the per-cell corner layout (8x the grid's bytes; skipped above the context's limit, 2 GiB
+    // unless a test set another with xrt_test_corner_grid_limit).  It is only an
     // acceleration: when the host copy or the device buffer cannot be had, the medium reads
     // the dense grid's rows instead (D.corners = null), with identical results.
     const size_t cx = m->nx - 1, cy = m->ny - 1, cz = m->nz - 1, cells = cx * cy * cz;
     free_buf(c->corners);
-    if (XRT_CORNER_GRID && cells && cells * 32 <= (size_t(2) << 30)) {
+    if (XRT_CORNER_GRID && cells && cells * 32 <= c->corner_limit) {
         std::vector<float> cor;
         try {
             cor.resize(cells * 8);
@@ -604,6 +605,15 @@ int xrt_set_medium(xrt_ctx* c, const xrt_medium_desc* m) {
 
 int xrt_set_medium_bricks(xrt_ctx* c, const xrt_medium_desc* m, const xrt_brick_grid* g) {
     return for_each_device(c, "xrt_set_medium_bricks", [&](xrt_ctx* d) { return set_medium_bricks_one(d, m, g); });
+}
+
+// a self-test's knob: where set_medium_one stops building the corner values, on every device
+int xrt_test_corner_grid_limit(xrt_ctx* c, uint64_t max_bytes) {
+    return for_each_device(c, "xrt_test_corner_grid_limit", [&](xrt_ctx* d) {
+        if (!d) return (int)XRT_ERR_INVALID;
+        d->corner_limit = (size_t)max_bytes;
+        return (int)XRT_OK;
+    });
 }
 
 }  // extern "C"

@@ -65,6 +65,8 @@ struct xrt_ctx {
     xrt::DevBuf q_rays, q_tmax, q_out;
     xrt::DevBuf brick_table, brick_data;   // sparse medium (xrt_set_medium_bricks)
     xrt::DevBuf corners;                   // dense medium: per-cell corner values (DMedium::corners)
+    // the most bytes the corner values may take; a larger grid reads its rows (xrt_test_corner_grid_limit)
+    size_t corner_limit = size_t(2) << 30;
     // guide buffers (xrt_render_aov): per object the albedo as uploaded (3 floats; DObj keeps
     // only albedo / PI), and the context's own planes (host output, sub-contexts of a multi render)
     xrt::DevBuf obj_albedo, aov;

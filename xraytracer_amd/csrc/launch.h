@@ -264,4 +264,11 @@ hipError_t launch_test_logexp(const float* x, uint32_t n, float* out, hipStream_
 hipError_t launch_test_powf(const float* x, uint32_t n, float y, float* out, hipStream_t st);
 hipError_t launch_test_fastdiv(uint32_t mode, float c, float rc, uint32_t first, uint32_t count,
                                unsigned long long* nbad, uint32_t* bad, hipStream_t st);
+// medium.h's medium_density of M at n points {x, y, z}
+hipError_t launch_test_density(const DMedium& M, const float* pts, uint32_t n, float* out, hipStream_t st);
+// medium.h's hg_sample / sample_wavelength over n items; item i draws from its own eight raw
+// stream words words[8 i ..], cursor 0
+hipError_t launch_test_hg(float g, const float* wo, const uint32_t* words, uint32_t n, float* wi, hipStream_t st);
+hipError_t launch_test_wavelength(const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
+                                  uint32_t* channel, float* pmf, hipStream_t st);
 }  // namespace xrt

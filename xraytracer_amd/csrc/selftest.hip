@@ -1,7 +1,9 @@
 // selftest.hip — device self-tests of the restated arithmetic (the RNG stream and its refill,
-// the glibc trigonometry / log / exp / pow, the fast divisions), run by the test suite against
-// the host's results.
+// the glibc trigonometry / log / exp / pow, the fast divisions) and of the medium's density
+// lookup and samplers (medium.h's own functions, not copies), run by the test suite against the
+// host's results.
 #include "launch.h"
+#include "medium.h"
 #include "path_common.h"
 
 namespace xrt {
@@ -98,6 +100,34 @@ __global__ void k_test_powf(const float* x, uint32_t n, float y, float* out) {
     if (i < n) out[i] = glibc_powf(x[i], y);
 }
 
+// medium_density of the medium M at pts[i] = {x, y, z}, one lane per point
+__global__ void k_test_density(DMedium M, const float* pts, uint32_t n, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = medium_density(M, mk(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
+}
+
+// hg_sample / sample_wavelength with the item's draws chosen by the caller: the stream is the
+// item's own eight raw (untempered) words, cursor 0
+__global__ void k_test_hg(float g, const float* wo, const uint32_t* words, uint32_t n, float* wi) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng rng{words + (size_t)i * 8, 0u};
+    v3 w;
+    hg_sample(g, mk(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), rng, w);
+    wi[3 * i] = w.x, wi[3 * i + 1] = w.y, wi[3 * i + 2] = w.z;
+}
+
+__global__ void k_test_wavelength(const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
+                                  uint32_t* channel, float* pmf) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Rng rng{words + (size_t)i * 8, 0u};
+    v3 p;
+    channel[i] = sample_wavelength(mk(thr[3 * i], thr[3 * i + 1], thr[3 * i + 2]),
+                                   mk(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2]), rng, p);
+    pmf[3 * i] = p.x, pmf[3 * i + 1] = p.y, pmf[3 * i + 2] = p.z;
+}
+
 hipError_t launch_test_rng(const uint32_t* seeds, uint32_t n_seeds, uint32_t skip, uint32_t n, float* out,
                            uint32_t* rings, hipStream_t st) {
     const uint32_t blocks = (n_seeds + kBlock - 1) / kBlock;
@@ -129,6 +159,22 @@ hipError_t launch_test_logexp(const float* x, uint32_t n, float* out, hipStream_
 
 hipError_t launch_test_powf(const float* x, uint32_t n, float y, float* out, hipStream_t st) {
     hipLaunchKernelGGL(k_test_powf, dim3((n + 255) / 256), dim3(256), 0, st, x, n, y, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_test_density(const DMedium& M, const float* pts, uint32_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_test_density, dim3((n + 255) / 256), dim3(256), 0, st, M, pts, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_test_hg(float g, const float* wo, const uint32_t* words, uint32_t n, float* wi, hipStream_t st) {
+    hipLaunchKernelGGL(k_test_hg, dim3((n + 255) / 256), dim3(256), 0, st, g, wo, words, n, wi);
+    return hipGetLastError();
+}
+
+hipError_t launch_test_wavelength(const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
+                                  uint32_t* channel, float* pmf, hipStream_t st) {
+    hipLaunchKernelGGL(k_test_wavelength, dim3((n + 255) / 256), dim3(256), 0, st, thr, albedo, words, n, channel, pmf);
     return hipGetLastError();
 }
 
