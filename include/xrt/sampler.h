@@ -2,7 +2,7 @@
 // 8-94, Src/sampler.cpp:3-12) for host code written against the reference API.  The same
 // libstdc++ std::mt19937 + uniform_real_distribution<float> as the reference, so a host
 // Sampler seeded j + width*i draws exactly the stream the GPU path draws for that pixel
-// (the device restates the generator: csrc/step_tri.hip k_refill_merged, path_common.h).
+// (the device restates the generator: csrc/refill.hip k_refill_merged, path_common.h).
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -74,7 +74,7 @@ static int check(const std::vector<int>& counts) {
     return 0;
 }
 
-// the device's split of pair j (merged_trace, step_tri.hip)
+// the device's split of pair j (merged_trace, merged.h)
 static uint32_t ray_of(uint32_t j, uint32_t c, uint32_t magic) {
     return c == 1u ? j : c == 2u ? j >> 1 : (uint32_t)(((uint64_t)j * magic) >> 32);
 }

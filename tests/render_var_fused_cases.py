@@ -20,7 +20,7 @@ MERGED, BVH, TRI, STEP = abi.XRT_SCHED_STEP_MERGED, abi.XRT_SCHED_STEP_BVH, abi.
 
 def two_quad_lights(w, h):
     """the Cornell box with a second quad light under its ceiling: two shadow rays per segment, so
-    GIIntegrator's NEE term is not folded at sampling time (step_tri.hip, kFold)"""
+    GIIntegrator's NEE term is not folded at sampling time (step_merged.h, kFold)"""
     s = scenes.SceneBundle()
     s.load_obj(scenes.CORNELL_OBJ)
     s.add_quad_light("QuadLight", (343.0, 548.0, 227.0), (343.0, 548.0, 332.0), (213.0, 548.0, 227.0), (25.0, 25.0, 25.0))

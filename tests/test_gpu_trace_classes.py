@@ -1,4 +1,4 @@
-"""The merged trace's class streams (merged_trace, xraytracer_amd/csrc/step_tri.hip) against the
+"""The merged trace's class streams (merged_trace, xraytracer_amd/csrc/merged.h) against the
 oracle: objects of equal triangle count rank their rays into one LDS stream and share its pair
 passes, a ranked ray carrying its object's first triangle.  Bar for every case: framebuffer bit for
 bit and the path counters equal to the oracle's, in full waves (64 slots per wave, the pair-pass

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """tools/isa_diff.py OLD.s NEW.s — are the kernels of OLD.s (tools/isa.sh of one unit at one commit) still
-in NEW.s (the same unit at another), instruction for instruction?
+in NEW.s (the same unit at another), instruction for instruction?  Either side may be several files
+joined by commas (code that moved between units: OLD.s NEW_A.s,NEW_B.s); a kernel that one side holds
+in two of its files counts as differing.
 
 A kernel's stream is every instruction line between its label and its .Lfunc_end, comments dropped and
 block labels renumbered in order of appearance; symbol names are left aside.  Kernels are paired by
@@ -48,8 +50,21 @@ def demangle(names):
     return dict(zip(names, (re.sub(r"\(.*$", "", r) for r in res)))   # the template-id; the argument list aside
 
 
+def kernels_of(paths, label):
+    """kernels() of comma-joined files as one dict; the mangled names found in more than one of them"""
+    out, twice = {}, []
+    for path in paths.split(","):
+        for k, v in kernels(path).items():
+            if k in out:
+                twice.append(k)
+            out[k] = v
+    for n in sorted(demangle(twice).values()):
+        print("twice   ", n, "in", label)
+    return out, len(twice)
+
+
 def main(old_path, new_path):
-    old, new = kernels(old_path), kernels(new_path)
+    (old, dup_old), (new, dup_new) = kernels_of(old_path, old_path), kernels_of(new_path, new_path)
     dn_old, dn_new = demangle(old), demangle(new)
     by_name = {}
     for k, n in dn_new.items():
@@ -57,7 +72,7 @@ def main(old_path, new_path):
         m = re.match(r"^(.*), false>$", n)
         if m:
             by_name.setdefault(m.group(1) + ">", k)
-    same = bad = 0
+    same, bad = 0, dup_old + dup_new
     for k, n in sorted(dn_old.items(), key=lambda q: q[1]):
         partner = by_name.get(n)
         if partner is None:
@@ -70,6 +85,8 @@ def main(old_path, new_path):
             same += 1
     paired = {by_name.get(n) for n in dn_old.values()}
     added = sorted(dn_new[k] for k in new if k not in paired)
+    for n in added:
+        print("new     ", n)
     print(f"{old_path} -> {new_path}: {same} kernels identical, {bad} differing or missing, {len(added)} new")
     return 1 if bad else 0
 

@@ -1,10 +1,11 @@
 #!/bin/bash
-# tools/regs.sh [pattern] — per-kernel VGPR/SGPR/spill/occupancy of $SRC (default step_tri.hip,
-# the merged kernels; SRC=step.hip, shade.hip, trace.hip, ... for the other units), gfx950; extra
+# tools/regs.sh [pattern] — per-kernel VGPR/SGPR/spill/occupancy of $SRC (default step_merged.hip,
+# the merged kernels' plain builds; SRC=step_merged_mom.hip, chunk_lists.hip, refill.hip, step.hip,
+# shade.hip, trace.hip, ... for the other units), gfx950; extra
 # -D flags in $REGS_DEFS
 cd "$(dirname "$0")/../xraytracer_amd/csrc"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -I../../include -I. --offload-arch=gfx950 \
-    $REGS_DEFS -c ${SRC:-step_tri.hip} -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 |
+    $REGS_DEFS -c ${SRC:-step_merged.hip} -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 |
 python3 -c '
 import re, sys
 pat = sys.argv[1] if len(sys.argv) > 1 else ""

@@ -1,7 +1,7 @@
 """tools/wave_timeline.py FILE [--launch N] [--simds 1024] [--cost-map] — the wave timeline of the merged step kernels.
 
 FILE is what an experiment build with -DXRT_PHASE_CLOCK=1 writes for a render when XRT_WAVE_CLOCK_OUT
-names it (step_tri.hip, wave_clock_dump): per wave the launch's group argument (all ones: a launch
+names it (step_merged.hip, wave_clock_dump): per wave the launch's group argument (all ones: a launch
 of every partition), the block, and the constant-rate wall clock and the shader clock at the wave's
 entry and exit.  Launches are told apart per group stream: a stream's launches do not overlap, so a
 wave that starts after every earlier wave of its stream has ended opens the next launch.

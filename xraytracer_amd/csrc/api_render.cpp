@@ -592,11 +592,8 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
         if (groups > 1) {
             if ((rc = GS.fork())) return rc;
             for (uint32_t g = 0; g < groups; ++g) {
-                const hipError_t e =
-                    R.mom ? launch_step_merged_mom(P, dP, c->step_objs, list, ci, out, co, cz, R.mom, R.step_visits,
-                                                   poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g])
-                          : launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
-                                               poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g]);
+                const hipError_t e = launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
+                                                        poll.live_hint, poll.live_part_max, groups, g, c->group_stream[g], R.mom);
                 if (e != hipSuccess) return hip_err(c, e, "k_step");
             }
             T.S.launches[XRT_K_STEP] += groups;
@@ -615,12 +612,9 @@ int run_fused(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists
         const hipError_t e = T.launch(XRT_K_STEP, [&] {
             if (spec_now)
                 return launch_step_spec(P, dP, list, ci, out, co, cz, R.spec_visits, poll.live_part_max, spw, c->stream);
-            if (R.merged && R.mom)
-                return launch_step_merged_mom(P, dP, c->step_objs, list, ci, out, co, cz, R.mom, R.step_visits,
-                                              poll.live_hint, poll.live_part_max, 1, 0, c->stream);
             if (R.merged)
                 return launch_step_merged(P, dP, c->step_objs, list, ci, out, co, cz, L.req(1), R.step_visits,
-                                          poll.live_hint, poll.live_part_max, 1, 0, c->stream);
+                                          poll.live_hint, poll.live_part_max, 1, 0, c->stream, R.mom);
             return launch_step(P, dP, list, ci, out, co, cz, L.req(1), R.step_visits, blocks, poll.live_hint, R.step_tri,
                                c->stream, R.mom);
         });

@@ -21,7 +21,7 @@ float bits(int x) {
 }
 
 // A triangle of an object lying in the plane x_a = c (e1_a = e2_a = 0 exactly) qualifies for
-// the exact plane cull (DObjPlane, plane_away in step_tri.hip) when the
+// the exact plane cull (DObjPlane, plane_away in merged.h) when the
 // Moller-Trumbore det and t numerator keep the sign of their exact values: with p, q the
 // other two axes, both reduce to (d_a resp. o_a - c) * (e1_p e2_q - e1_q e2_p), each product
 // rounded twice and the difference once, so |A - B| must exceed a few ulps of |A| + |B|.

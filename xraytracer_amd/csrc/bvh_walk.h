@@ -117,7 +117,7 @@ __device__ bool bvh_trace(const KParams& P, const f4* top, int ntop, SE* stk, v3
     return false;
 }
 
-// Two-level scenes: the small objects' plane cull (DObjPlane, wavefront.h; step_tri.hip plane_away)
+// Two-level scenes: the small objects' plane cull (DObjPlane, wavefront.h; merged.h plane_away)
 __device__ __forceinline__ bool plane_away_w(v3 o, v3 d, const DObjPlane& pl) {
     const float oa = pl.axis == 0 ? o.x : (pl.axis == 1 ? o.y : o.z);
     const float da = pl.axis == 0 ? d.x : (pl.axis == 1 ? d.y : d.z);

@@ -109,16 +109,14 @@ hipError_t launch_step(const KParams& P, const KParams* dP, const uint32_t* list
                        uint32_t* out_count, uint32_t* zero, uint32_t* req_count, uint32_t visits, uint32_t blocks,
                        uint64_t live, bool tri, hipStream_t st, float2* mom = nullptr);
 
-// ------------------------------------------------------------------- step_tri.hip ----
+// --------------------------------------------------------------------- refill.hip ----
 // twist the rings of the slots on P.req (count at *count); clears *zero_count
 hipError_t launch_refill(const KParams& P, const uint32_t* count, uint32_t* zero_count, hipStream_t st);
-// the merged schedule's refill (leaves ST_RNGREQ to the merged kernel; see step_tri.hip)
+// the merged schedule's refill (leaves ST_RNGREQ to the merged kernel; see refill.hip)
 hipError_t launch_refill_merged(const KParams& P, const uint32_t* count, uint32_t* zero_count, hipStream_t st);
-// phase A of a two-level trace with the small objects traced by the merged pair passes
-// (launch_trace calls it when P.sstep is set; the one-light or kMaxLights build, as launch_trace's)
-hipError_t launch_trace_2a_coop(const KParams& P, const uint32_t* list, const uint32_t* count, uint32_t* zero,
-                                uint32_t blocks, hipStream_t st);
-// merged-trace triangle schedule: eligibility, RNG words one segment may
+
+// ---------------------------------------------------------------- step_merged.hip ----
+// merged-trace triangle schedule (the kernels: step_merged.h): eligibility, RNG words one segment may
 // draw, LDS bytes, and the launch (same list / counter contract as launch_step; SO: the
 // kernel-argument object records, build_step_objs in wavefront.h)
 bool use_step_merged(const KParams& P);
@@ -130,16 +128,11 @@ size_t step_merged_lds_bytes(const KParams& P);
 // groups, group: the launch serves the partitions of group `group` of `groups` only (step_groups.h:
 // their lists, their counters in out_count and zero); 1, 0: every partition.  live and
 // live_part_max are the whole shard's either way
+// mom: as launch_shade's (the moments builds, a unit of their own: step_merged_mom.hip)
 hipError_t launch_step_merged(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
                               const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
                               uint32_t* req_count, uint32_t visits, uint64_t live, uint32_t live_part_max,
-                              uint32_t groups, uint32_t group, hipStream_t st);
-// ... and its moments builds (a unit of their own, step_tri.hip as step_tri_mom.o): the slots' {s1, s2}
-// records, as launch_shade's mom, in req_count's place
-hipError_t launch_step_merged_mom(const KParams& P, const KParams* dP, const StepObjs& SO, const uint32_t* list,
-                                  const uint32_t* count, uint32_t* out, uint32_t* out_count, uint32_t* zero,
-                                  float2* mom, uint32_t visits, uint64_t live, uint32_t live_part_max,
-                                  uint32_t groups, uint32_t group, hipStream_t st);
+                              uint32_t groups, uint32_t group, hipStream_t st, float2* mom = nullptr);
 // The whole-wave phase in block-owned chunks (step_chunks.h).  The chunk buffer: header words (chunks
 // and live slots per class), the partitions' live counts without the retired pixels, two counters
 // per chunk and two segments of kChunkSlots entries per chunk, for 8 * class_cap chunks.
@@ -148,21 +141,23 @@ struct ChunkBufs {
     uint32_t class_cap;
     uint32_t chunks, blocks;   // after the build: chunks that hold a slot; blocks of a launch of the phase (0: the phase does not run)
 };
-// the chunks from the seeded partition lists (header and counters cleared by the caller before)
-hipError_t launch_chunks_build(const KParams& P, const ChunkBufs& B, const uint32_t* list, const uint32_t* count,
-                               hipStream_t st);
 // one launch of the phase, numbered rot: `passes` passes of `visits` visits per block; adds the live
 // slots left to live_count (n_part words, cleared before) and clears zero, as a step launch does
 hipError_t launch_step_merged_chunks(const KParams& P, const KParams* dP, const StepObjs& SO, const ChunkBufs& B,
                                      uint32_t* live_count, uint32_t* zero, uint32_t visits, uint32_t passes, uint32_t rot,
                                      hipStream_t st);
-// the chunks' live slots onto the partition lists `out` (counters out_count, cleared before)
-hipError_t launch_chunks_scatter(const KParams& P, const ChunkBufs& B, uint32_t* out, uint32_t* out_count, hipStream_t st);
 #if XRT_PHASE_CLOCK
 // experiment builds: the merged kernels' per-wave entry / exit clocks of the work queued on st so far,
 // written to `path` (null: dropped) and cleared; tools/wave_timeline.py reads the file
 hipError_t wave_clock_dump(const char* path, hipStream_t st);
 #endif
+
+// ---------------------------------------------------------------- chunk_lists.hip ----
+// the chunks from the seeded partition lists (header and counters cleared by the caller before)
+hipError_t launch_chunks_build(const KParams& P, const ChunkBufs& B, const uint32_t* list, const uint32_t* count,
+                               hipStream_t st);
+// the chunks' live slots onto the partition lists `out` (counters out_count, cleared before)
+hipError_t launch_chunks_scatter(const KParams& P, const ChunkBufs& B, uint32_t* out, uint32_t* out_count, hipStream_t st);
 
 // ----------------------------------------------------------------------- spec.hip ----
 // speculative sample starts for the merged schedule's group layouts: eligibility,

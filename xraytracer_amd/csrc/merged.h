@@ -1,7 +1,7 @@
-// merged.h — helpers shared by the merged-trace kernels (step_tri.hip: k_step_merged,
+// merged.h — helpers shared by the merged-trace kernels (step_merged.h: k_step_merged; trace.hip:
 // k_trace_2a_coop; spec.hip: k_step_spec): global-address-space loads, the exact plane cull,
-// the branch-free Moller-Trumbore test and the group trace (G lanes per slot split a slot's
-// candidate triangles).  Device code only.
+// the branch-free Moller-Trumbore test, the group trace (G lanes per slot split a slot's
+// candidate triangles) and the pair-pass trace of the whole wave (merged_trace).  Device code only.
 #pragma once
 #include "path_common.h"
 
@@ -299,5 +299,113 @@ struct MergedWave {
     unsigned long long best[64];       // closest hit of the extension ray: (t bits << 32) | tri
     uint32_t occ[64];                  // bit l: shadow ray l is occluded
 };
+
+// One cooperative trace of the wave: the extension ray (closest hit, if `ext`) and the
+// pending shadow rays (any hit, bits of `shm`).  ORIG: the closest-hit key's low word is the
+// triangle's original index (the w of its third float4, KParams::stri) instead of its LDS
+// index — two-level scenes, whose BVH walk merges in the same (t, original index) order.
+template <int NL, bool ORIG = false>
+__device__ __forceinline__ void merged_trace(const StepObjs& SO, const LScene& L, MergedWave<NL>& W, int lane,
+                                             bool ext, v3 o, v3 d, uint32_t shm, const v3 (&so)[NL + 1],
+                                             const v3 (&sd)[NL + 1], const float (&stm)[NL + 1],
+                                             unsigned long long& best, uint32_t& occ
+) {
+    constexpr int R = 1 + NL;
+    W.best[lane] = ~0ull;
+    W.occ[lane] = 0u;
+    v3 inv[R], oi[R];
+    inv[0] = rcp3c(d);
+    oi[0] = o * inv[0];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) inv[1 + l] = rcp3c(sd[l]), oi[1 + l] = so[l] * inv[1 + l];
+    wave_sync();
+    constexpr uint32_t kCap = R * 64;   // ranked rays W.ro / W.rd hold
+    for (int ci = 0; ci < SO.n_cls; ++ci) {
+        const StepClass K = SO.cls[ci];
+#if XRT_TRACE_TLIM
+        // the classes so far: an extension ray skips an object whose box it enters beyond its
+        // closest hit (every triangle inside lies deeper than the box margin, far above the
+        // float error of either t; ties are still tested), a shadow ray one it is occluded by.
+        // Read once per class: its objects do not cull each other.
+        const unsigned long long cur = W.best[lane];
+        const float bt = cur == ~0ull ? kINF : __uint_as_float((uint32_t)(cur >> 32));
+        const uint32_t done = W.occ[lane];
+#else
+        const float bt = kINF;
+        const uint32_t done = 0u;
+#endif
+        const uint32_t c = K.c, magic = K.magic;
+        // the pair passes over the `tot` rays ranked so far: one (ray, triangle) pair per lane
+        // and step, pair j -> ray j / c and triangle j % c of that ray's object; an
+        // out-of-range lane of the last step tests the last pair again with its result dropped
+        // (no divergent branch; two steps per iteration with both tests before the merges
+        // measured 5% slower on C2)
+        auto passes = [&](uint32_t tot) {
+            wave_sync();
+            const uint32_t pairs = tot * c;
+            for (uint32_t j0 = 0; j0 < pairs; j0 += 64u) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                const bool valid = j < pairs;
+                const uint32_t jj = valid ? j : pairs - 1u;
+                const uint32_t r = c == 1u ? jj : c == 2u ? jj >> 1 : __umulhi(jj, magic);
+                const f4 D = W.rd[r];
+                const f4 A = W.ro[r];
+                const uint32_t e = __float_as_uint(D.w) & (kRayIds - 1u);
+                const uint32_t k = (__float_as_uint(D.w) >> kRayIdBits) + (jj - r * c);
+                const f4 C = L.tri[3 * k + 2];
+                float t;
+                if (ray_tri_nb(xyz(A), xyz(D), xyz(L.tri[3 * k]), xyz(L.tri[3 * k + 1]), xyz(C), t) && valid) {
+                    if (e < 64u)
+                        atomicMin(&W.best[e], ((unsigned long long)__float_as_uint(t) << 32) | (ORIG ? __float_as_uint(C.w) : k));
+                    else if (t < A.w)
+                        atomicOr(&W.occ[e & 63u], 1u << ((e >> 6) - 1u));
+                }
+            }
+            wave_sync();
+        };
+        // the rays themselves are ranked into W (not their ids), so a pair reads its ray
+        // with one LDS access instead of an id and then the ray; a ray's record carries its
+        // object's first triangle above its id.  An object whose rays would not fit behind
+        // those ranked already waits for their passes and is then ranked from 0.
+        uint32_t tot = 0;
+        for (uint32_t ob = K.begin; ob < K.end || tot;) {
+            bool full = ob == K.end;   // wave-uniform: run the passes now (the class's last rays, or no room)
+            if (!full) {
+                const StepObj B = SO.o[ob];
+                bool need[R];
+                need[0] = ext && !plane_away(o, d, B.axis, B.plane) && obj_overlap(oi[0], inv[0], B, bt);
+#pragma unroll
+                for (int l = 0; l < NL; ++l)
+                    need[1 + l] = B.occluder && ((shm & ~done) >> l & 1u) && !plane_away(so[l], sd[l], B.axis, B.plane) &&
+                                  obj_overlap(oi[1 + l], inv[1 + l], B, stm[l]);
+                uint64_t m[R];
+                uint32_t n_ob = 0;
+#pragma unroll
+                for (int q = 0; q < R; ++q) m[q] = __ballot(need[q]), n_ob += (uint32_t)__popcll(m[q]);
+                full = tot + n_ob > kCap;   // then tot > 0, since n_ob <= kCap: the object is ranked next time round
+                if (!full) {
+                    const uint32_t tag = (uint32_t)B.first << kRayIdBits;
+#pragma unroll
+                    for (int q = 0; q < R; ++q) {
+                        if (need[q]) {
+                            const uint32_t at = tot + lanemask_rank(m[q]);
+                            const v3 ro = q == 0 ? o : so[q - 1], rd = q == 0 ? d : sd[q - 1];
+                            W.ro[at] = make_float4(ro.x, ro.y, ro.z, q == 0 ? kINF : stm[q - 1]);
+                            W.rd[at] = make_float4(rd.x, rd.y, rd.z, __uint_as_float(tag | (uint32_t)(q * 64 + lane)));
+                        }
+                        tot += (uint32_t)__popcll(m[q]);
+                    }
+                    ++ob;
+                }
+            }
+            if (full) {
+                passes(tot);
+                tot = 0;
+            }
+        }
+    }
+    best = W.best[lane];
+    occ = W.occ[lane];
+}
 
 }  // namespace xrt

@@ -1,5 +1,5 @@
 // path_common.h — device building blocks shared by the path-tracing kernels
-// (shade.hip + trace.hip: wavefront schedule; step.hip: fused schedules; step_tri.hip:
+// (shade.hip + trace.hip: wavefront schedule; step.hip: fused schedules; step_merged.h:
 // merged-trace triangle schedule): the mt19937 stream restatement, wave utilities,
 // ray/primitive tests, light and BSDF sampling, the camera, the steps of the renderer's sample
 // loop every schedule repeats, and the LDS scene carve of the fused schedules.
@@ -531,7 +531,7 @@ __device__ __forceinline__ bool root_overlap(const f4& n0, const f4& n1, const f
     return l || r;
 }
 
-// rcp3 clamped to +-1e30 (the fma-form culling slabs, step_tri.hip obj_overlap)
+// rcp3 clamped to +-1e30 (the fma-form culling slabs, merged.h obj_overlap)
 __device__ __forceinline__ float rcpc(float x) {
     return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(x), -1e30f, 1e30f);
 }

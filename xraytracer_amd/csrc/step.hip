@@ -2,7 +2,7 @@
 // (lscene.h), the path state in registers for `visits` segments per launch.
 //   k_step     : one ray per lane; every scene kind and integrator, media included (medium.h)
 //   k_step_tri : small triangle scenes (GI / Direct) with cooperative traces (coop_trace)
-// The merged-trace triangle schedule (step_tri.hip) and its speculative variant (spec.hip)
+// The merged-trace triangle schedule (step_merged.h) and its speculative variant (spec.hip)
 // take the scenes they are eligible for before these two.
 #include <type_traits>
 

@@ -6,7 +6,7 @@
 // append the surviving slots to the chunk's other segment and meet at a barrier.  Within one launch
 // a chunk is served by one block only, which runs a fixed number of passes over the chunks it owns
 // and exits; no block waits for another, and a launch has no tail of late-starting waves, because
-// the grid never exceeds the wave slots of the GPU (k_step_merged_chunks, step_tri.hip).
+// the grid never exceeds the wave slots of the GPU (k_step_merged_chunks, step_merged.h).
 //
 // Chunks are numbered c = 8 j + x: x = c % 8 is the chunk's class, the residue of the partitions
 // whose live lists were concatenated into it (k_chunks_build) and of the blocks that serve it, so a

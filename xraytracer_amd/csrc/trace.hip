@@ -3,16 +3,17 @@
 //   k_trace       : the linear primitive array, staged through LDS in tiles shared by the block
 //   k_trace_small : small triangle scenes, the whole scene in LDS, per-object box culling
 //   k_trace_bvh   : large triangle scenes through the host-built BVH (bvh.h, bvh_walk.h)
-//   k_trace_2a, k_trace_deep4, k_trace_deep4q : the two-level trace (small objects, then the
-//                   BVH walk of the queued rays alone)
+//   k_trace_2a, k_trace_2a_coop, k_trace_deep4, k_trace_deep4q : the two-level trace (small
+//                   objects, then the BVH walk of the queued rays alone)
 // What these kernels share is defined once in trace_common.h (the slot ray load, the small-object
-// scan, phase A's tail, phase B's queue view and ray fetch; k_trace_2a_coop in step_tri.hip uses
-// the same) and bvh_walk.h (the BVH's share of LDS, the per-lane walk).
+// scan, phase A's tail, phase B's queue view and ray fetch) and bvh_walk.h (the BVH's share of LDS,
+// the per-lane walk); k_trace_2a_coop's pair passes are the merged step kernels' (merged.h).
 // The ray queries (xrt_query) run through the same kernels: k_query_in turns the caller's rays
 // into slots, launch_trace traces them, k_query_out rebuilds IntersectInfo from the records.
 #include "bvh.h"
 #include "bvh_walk.h"
 #include "launch.h"
+#include "merged.h"
 #include "path_common.h"
 #include "trace_common.h"
 
@@ -205,6 +206,42 @@ __global__ __launch_bounds__(kBlock) void k_trace_2a(KParams P, const uint32_t* 
         SlotHit H;
         small_scan<true, true>(R, inv, ltri, lbox, lpl, P.n_sobj, H);
         phase_a_finish(P, A, R, inv, H, lane);
+    }
+}
+
+// k_trace_2a with the small objects traced by merged_trace's object-major
+// pair passes (merged.h) instead of a per-lane object loop: one wave = 64 slots, their extension ray
+// and shadow rays, the small objects' triangles in LDS (KParams::stri, iteration order, so
+// the (t bits << 32 | local index) minimum is the (t, original index) minimum).  The winner's
+// (t, u, v) are recomputed with Mesh::rayTriangleIntersect's ops as the merged kernel does;
+// rays whose segment reaches the BVH root are queued for k_trace_deep.
+template <int NL>
+__global__ __launch_bounds__(kBlock, XRT_2A_WAVES) void k_trace_2a_coop(KParams P, const StepObjs SO, const uint32_t* __restrict__ list,
+                                                          const uint32_t* __restrict__ count, uint32_t* zero_count) {
+    extern __shared__ __attribute__((aligned(16))) f4 lds_2c[];
+    LScene L;
+    L.tri = lds_2c;
+    MergedWave<NL>* Wv = reinterpret_cast<MergedWave<NL>*>(lds_2c + 3 * P.n_stri);
+    const int tid = threadIdx.x, lane = tid & 63;
+    MergedWave<NL>& W = Wv[tid >> 6];
+    lds_copy(const_cast<f4*>(L.tri), P.stri, 3 * P.n_stri, tid);
+    zero_parts(P, zero_count);
+    __syncthreads();
+    const PartIter it = part_iter(P, count, kBlock);
+    const PhaseA A = phase_a_begin(P, it);
+    for (uint32_t base = it.first; base < it.n; base += it.stride) {
+        const SlotRays<NL, NL + 1> R = load_slot_rays<NL, NL + 1>(P, list, it, base + tid);
+        unsigned long long best;
+        SlotHit H;
+        merged_trace<NL>(SO, L, W, lane, R.want, R.o, R.d, R.smask, R.so, R.sd, R.stmax, best, H.occ);
+        if (R.want && best != ~0ull) {
+            const int hk = (int)(uint32_t)best;
+            (void)ray_tri(R.o, R.d, xyz(L.tri[3 * hk]), xyz(L.tri[3 * hk + 1]), xyz(L.tri[3 * hk + 2]), H.t, H.u, H.v);
+            H.k = __float_as_int(L.tri[3 * hk + 2].w);
+        }
+        H.occ &= R.smask;
+        phase_a_finish(P, A, R, rcp3(R.d), H, lane);
+        wave_sync();   // W is rewritten by the next round's rays
     }
 }
 
@@ -512,10 +549,12 @@ hipError_t launch_trace(const KParams& P, const uint32_t* list, const uint32_t* 
                 if (e != hipSuccess) return e;
                 const size_t lds_a =
                     (size_t)P.n_stri * 3 * sizeof(f4) + (size_t)P.n_sobj * (sizeof(DObjBox) + sizeof(DObjPlane));
-                if (P.sstep)
-                    e = launch_trace_2a_coop(P, list, count, zero, blocks, st);
-                else
+                if (P.sstep) {   // the small objects by the merged pair passes
+                    const size_t lds_c = (size_t)P.n_stri * 3 * sizeof(f4) + (kBlock / 64) * sizeof(MergedWave<NL>);
+                    hipLaunchKernelGGL((k_trace_2a_coop<NL>), dim3(blocks), dim3(kBlock), lds_c, st, P, *P.sstep, list, count, zero);
+                } else {
                     hipLaunchKernelGGL((k_trace_2a<NL>), dim3(blocks), dim3(kBlock), lds_a, st, P, list, count, zero);
+                }
                 if (e == hipSuccess) e = hipGetLastError();
                 return e;   // phase B: launch_trace_deep
             }

@@ -1,4 +1,4 @@
-// trace_common.h — the steps the trace kernels share (trace.hip; step_tri.hip k_trace_2a_coop):
+// trace_common.h — the steps the trace kernels share (trace.hip, k_trace_2a_coop included):
 //   SlotRays / load_slot_rays : a slot's extension ray and shadow rays          (k_trace, k_trace_small,
 //                                                                                k_trace_2a, k_trace_2a_coop)
 //   SlotHit / write_slot_hit  : the closest hit and occlusion mask of a slot    (k_trace_small, phase A)

@@ -101,7 +101,7 @@ struct DObjBox {
     float bmax[3];
     int count_occ;   // triangle count | (occluder << 31)
 };
-// Per-object record of the merged-trace triangle kernel (step_tri.hip), passed by value
+// Per-object record of the merged-trace triangle kernel (step_merged.h), passed by value
 // as a kernel argument so the object loop reads it with scalar loads: the culling box
 // (DObjBox's, margin included), its first triangle (their count is its class's, StepClass),
 // and whether it occludes (no area light).
@@ -117,7 +117,7 @@ struct StepObj {
 // axis `axis` (-1: no such plane).  Every Moller-Trumbore test of such an object by a ray
 // whose origin lies on one side of the plane and whose direction does not point back at it
 // returns t <= 0 (or |det| < eps), so the merged-trace kernels skip the object for that ray
-// without a box test (plane_away, step_tri.hip; the argument is in DESIGN.md §3).
+// without a box test (plane_away, merged.h; the argument is in DESIGN.md §3).
 struct DObjPlane {
     int axis;
     float c;
