@@ -51,6 +51,7 @@ struct FlatScene {
     std::vector<int> tri_first;      // per object: its first triangle (-1: not a mesh)
     double emax = 0.0;               // largest |e1| |e2| of a triangle (bounds |det| of every ray test)
     bool has_mirror = false, has_glass = false;
+    bool all_lambert = true;         // every object that is no light is a Lambert (use_step_spec)
 
     // object k's flags in DObjBox::count_occ
     int count_occ(size_t k) const { return obj_count[k] | (objs[k].light < 0 ? (int)0x80000000 : 0); }
@@ -72,6 +73,7 @@ int flatten_scene(xrt_ctx* c, const xrt_scene_desc* s, FlatScene& F) {
         const xrt_object& o = s->objects[k];
         F.has_mirror = F.has_mirror || o.material == XRT_MAT_METAL || o.material == XRT_MAT_GLASS;
         F.has_glass = F.has_glass || o.material == XRT_MAT_GLASS;
+        F.all_lambert = F.all_lambert && (o.light >= 0 || o.material == XRT_MAT_LAMBERT);
         if (o.light >= (int)s->n_lights || o.count < 0 || o.first < 0)
             return set_err(c, XRT_ERR_INVALID, "object " + std::to_string(k) + ": bad light index or range");
         DObj d{};
@@ -192,6 +194,7 @@ int upload_flat(xrt_ctx* c, const FlatScene& F) {
     // so below 2^120 every finite det is either < kEPSILON (rejected whatever 1/det is) or in
     // rcp_newton's exact range: ray_tri_nb then skips the IEEE fallback (det_bounded).
     P.det_bounded = F.emax < 0x1p120 ? 1 : 0;   // NaN / inf edges: false
+    P.all_lambert = F.all_lambert ? 1 : 0;
     return XRT_OK;
 }
 

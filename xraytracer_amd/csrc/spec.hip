@@ -572,10 +572,15 @@ __global__ __launch_bounds__(kBlock, XRT_STEP_WAVES) void k_step_spec(
 
 // ------------------------------------------------------------------- host side ----
 // GIIntegrator with one area light and maxDepth >= 2 over a merged-schedule triangle scene of
-// at most 64 triangles (the camera lists' masks; the group traces' masks need the same)
+// at most 64 triangles (the camera lists' masks; the group traces' masks need the same) in which
+// every object that is no light is a Lambert (KParams::all_lambert, found at the upload): the
+// candidate offsets 0, 1 and 5 are the words a sample can have drawn when it ends on such a
+// scene — a hit at the last depth draws rr + 4.  On an object without a material it draws
+// rr + 2 (Object::sampleBxDF draws nothing), an offset no lane holds, so such scenes keep
+// k_step_merged in the group layouts: the same bits.
 bool use_step_spec(const KParams& P) {
     return P.scene_kind == SCN_TRI && P.integrator == XRT_INTEGRATOR_GI && P.n_lights == 1 && P.max_depth >= 2 &&
-           P.n_tris <= 64 && !(P.rflags & XRT_FLAG_NO_GROUP) && use_step_merged(P);
+           P.n_tris <= 64 && P.all_lambert && !(P.rflags & XRT_FLAG_NO_GROUP) && use_step_merged(P);
 }
 
 hipError_t launch_camlist(const KParams& P, bool retire, hipStream_t st) {

@@ -239,6 +239,7 @@ struct KParams {
     const f4* sblk;           // per 64 ssph entries: a ball (center, radius) holding each member's ball of radius |r| + sph_pad
     int n_segs, n_lights, n_tris, n_sph, n_box, scene_kind, n_objs, small_tri;
     int det_bounded;   // every triangle has |e1| |e2| < 2^120 (ray_tri_nb's Newton reciprocal, api_scene.cpp)
+    int all_lambert;   // every object that is no light has a Lambert material (use_step_spec; host only)
     DMedium medium;
     // ---- camera (row-major c2w) + PinholeCamera scale / aspect
     float c2w[16];

@@ -83,7 +83,7 @@ class HipRenderer:
         current contents before the divide (XRT_FLAG_ACCUMULATE, Renderer::render's contract).
         deep: the two-level trace's BVH walk, "auto", "single" (one lane per queued ray) or
         "quad" (four); results never depend on it.  spec: speculative sample starts in the merged
-        schedule's 16-slot launches (GI with one light; spec=False sets XRT_FLAG_NO_SPEC); results
+        schedule's 16-slot launches (GI with one light, every other object a Lambert; spec=False sets XRT_FLAG_NO_SPEC); results
         never depend on it.  whitted_bvh: WhittedIntegrator may render a triangle scene that does
         not fit LDS through its triangle BVH (XRT_FLAG_WHITTED_BVH, XRT_SCHED_WHITTED_BVH) instead
         of refusing it; a scene that fits LDS renders as without it.  overlap: the merged schedule's
