@@ -391,6 +391,28 @@ __device__ __forceinline__ ChunkIter chunk_iter(const uint32_t* hdr, uint32_t* c
     __syncthreads();
     return K;
 }
+// The block's issue priority for its next pass.  A SIMD serves its oldest wave first, and the blocks of
+// a launch are dispatched in index order, one per CU and round: the block's quarter of the grid is the
+// age rank of its waves among the four on their SIMD (the wave timeline: a pass of the first quarter's
+// blocks takes 0.6 of the last quarter's), so the old blocks end a launch early and the young ones
+// finish it on a GPU a quarter to three quarters empty.  With XRT_CHUNK_PRIO every block takes each of
+// the four priority levels in turn, pass after pass, starting at its rank: over four passes the waves
+// of a SIMD get equal shares.  The level is block-uniform, so the block's barriers set no wave against
+// another.  Where the dispatch order is another, or the grid smaller than the GPU, the levels still
+// rotate and only the start is arbitrary: results never depend on it.  The kernel ends after its last
+// pass, so no other code runs at a raised level.
+__device__ __forceinline__ void chunk_priority(uint32_t left) {
+#if XRT_CHUNK_PRIO
+    switch ((4u * blockIdx.x / gridDim.x - left) & 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
+#else
+    (void)left;
+#endif
+}
 // the block's next pass: round robin over its chunks that still have live slots; false: none, or no pass left
 __device__ __forceinline__ bool chunk_next(ChunkIter& K) {
     if (K.left == 0u) return false;
@@ -403,6 +425,7 @@ __device__ __forceinline__ bool chunk_next(ChunkIter& K) {
             K.h = v >> 16, K.n = v & 0xffffu;
             K.t = t;
             --K.left;
+            chunk_priority(K.left);
             return true;
         }
     }

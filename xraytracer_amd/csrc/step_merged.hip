@@ -10,22 +10,29 @@ namespace xrt {
 
 #if XRT_PHASE_CLOCK
 hipError_t wave_clock_dump(const char* path, hipStream_t st) {
-    unsigned int n = 0, zero = 0;
+    unsigned int n = 0, m = 0, zero = 0;
     int khz = 0, dev = 0;
     hipError_t e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_wave_clock_n), sizeof(n));
     if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_wave_clock_n), &zero, sizeof(zero));
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(&m, HIP_SYMBOL(g_pass_clock_n), sizeof(m));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_pass_clock_n), &zero, sizeof(zero));
     if (e == hipSuccess) e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
     if (e != hipSuccess || !path) return e;
     n = std::min(n, kWaveClockCap);
     std::vector<WaveClockRec> rec(n);
     if (n) e = hipMemcpyFromSymbol(rec.data(), HIP_SYMBOL(g_wave_clock), (size_t)n * sizeof(WaveClockRec));
+    m = std::min(m, kPassClockCap);
+    std::vector<PassClockRec> pass(m);   // the chunk kernel's pass ends (step_sources.h)
+    if (m && e == hipSuccess) e = hipMemcpyFromSymbol(pass.data(), HIP_SYMBOL(g_pass_clock), (size_t)m * sizeof(PassClockRec));
     if (e != hipSuccess) return e;
-    if (FILE* f = std::fopen(path, "wb")) {   // header: record count, wall clock kHz; then the records
+    if (FILE* f = std::fopen(path, "wb")) {   // header: record count, wall clock kHz; then the records; then the pass ends likewise
         const uint32_t head[2] = {n, (uint32_t)khz};
         std::fwrite(head, sizeof(head), 1, f);
         std::fwrite(rec.data(), sizeof(WaveClockRec), n, f);
+        std::fwrite(&m, sizeof(m), 1, f);
+        std::fwrite(pass.data(), sizeof(PassClockRec), m, f);
         std::fclose(f);
     }
     return hipSuccess;

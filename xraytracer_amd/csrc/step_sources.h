@@ -76,12 +76,42 @@ struct OneGroup : PartSlots {
     }
 };
 
+// Experiment builds (XRT_PHASE_CLOCK, tools/wave_timeline.py --chunks): lane 0 of every wave of the
+// chunk kernel records the wall clock before and after each barrier of a pass end, with the
+// survivors the wave counted in that pass; wave_clock_dump writes the records behind the waves'.
+// kind 0: the barrier of the append (the waves' counts meet), 1: the barrier that ends the pass.
+#if XRT_PHASE_CLOCK
+constexpr uint32_t kPassClockCap = 1u << 19;
+struct PassClockRec {
+    uint32_t block, wave_kind, n, pad;   // wave_kind: wave of the block | kind << 8
+    unsigned long long before, after;
+};
+static __device__ PassClockRec g_pass_clock[kPassClockCap];
+static __device__ unsigned int g_pass_clock_n;
+__device__ __forceinline__ uint32_t pass_clock_before(uint32_t kind, uint32_t n, int tid) {
+    uint32_t idx = kPassClockCap;
+    if ((tid & 63) == 0) {
+        idx = atomicAdd(&g_pass_clock_n, 1u);
+        if (idx < kPassClockCap) {
+            g_pass_clock[idx].block = blockIdx.x, g_pass_clock[idx].wave_kind = (uint32_t)(tid >> 6) | kind << 8;
+            g_pass_clock[idx].n = n, g_pass_clock[idx].pad = 0;
+            g_pass_clock[idx].before = wall_clock64();
+        }
+    }
+    return idx;
+}
+__device__ __forceinline__ void pass_clock_after(uint32_t idx) {
+    if (idx < kPassClockCap) g_pass_clock[idx].after = wall_clock64();
+}
+#endif
+
 // The chunk phase (k_step_merged_chunks; step_chunks.h): the chunks this block owns in the launch
 // numbered rot, over ChunkIter and its steps (path_common.h).  A pass runs one chunk: its survivors go
 // to the chunk's other segment, and the block meets at a barrier before the next.  Whole waves of
 // one-level scenes, plain renders.  The kernel hands the body visits | passes << 8 for `visits` (both
 // at most 255, launch_step_merged_chunks): begin and visits take them apart.  (Passed as a member of
 // their own the passes cost every chunk kernel its instruction stream, DESIGN.md.)
+constexpr uint32_t kChunkClockTag = 0xFFFFFFFEu;   // the chunk kernel's waves in the wave clock records (~0: every partition)
 struct OwnedChunks {
     const uint32_t* hdr;   // k_chunks_build's header (chunks per class)
     uint32_t *cnt, *seg;   // the chunks' counters and segments
@@ -90,7 +120,7 @@ struct OwnedChunks {
     using Pass = ChunkIter;
     template <int SPW, int G, bool LANE, bool BVH, bool MOM>
     static constexpr bool layout_ok() { return SPW == 64 && G == 1 && !LANE && !BVH && !MOM; }
-    __device__ __forceinline__ uint32_t clock_tag() const { return ~0u; }
+    __device__ __forceinline__ uint32_t clock_tag() const { return kChunkClockTag; }
     __device__ __forceinline__ void clear(const KParams& P) const { zero_parts(P, zero_count); }
     __device__ __forceinline__ Pass begin(const KParams&, uint32_t, uint32_t arg) const {
         return chunk_iter(hdr, cnt, seg, rot, arg >> 8);
@@ -104,9 +134,23 @@ struct OwnedChunks {
         return glb<gu32>(K.seg + (size_t)(2u * K.c + K.h) * kChunkSlots)[i];
     }
     __device__ __forceinline__ void append(const KParams&, Pass& K, bool want, uint32_t s, int lane, int tid) const {
+#if XRT_PHASE_CLOCK
+        const uint32_t ck = pass_clock_before(0u, (uint32_t)__popcll(__ballot(want)), tid);
+#endif
         chunk_append(K, want, s, lane, tid);
+#if XRT_PHASE_CLOCK
+        pass_clock_after(ck);
+#endif
     }
-    __device__ __forceinline__ void pass_end() const { chunk_pass_end(); }
+    __device__ __forceinline__ void pass_end() const {
+#if XRT_PHASE_CLOCK
+        const uint32_t ck = pass_clock_before(1u, 0u, (int)threadIdx.x);
+#endif
+        chunk_pass_end();
+#if XRT_PHASE_CLOCK
+        pass_clock_after(ck);
+#endif
+    }
     // the live slots the block's chunks are left with, summed over the launch's blocks
     __device__ __forceinline__ void finish(const KParams& P, const Pass& K) const {
         const uint32_t left = chunk_live(K);

@@ -40,6 +40,9 @@
 #ifndef XRT_CHUNK_PASSES
 #define XRT_CHUNK_PASSES 4   // the whole-wave phase in block-owned chunks (step_chunks.h): passes per block per launch of k_step_merged_chunks, and the passes a render must have samples for to take the phase by the rule (C2, profiles/r11_c2_bench.json: 0, the phase off, 45.22 ms as the parent's 45.31; 4: 42.75; 8: 43.01; 10: 43.17)
 #endif
+#ifndef XRT_CHUNK_PRIO
+#define XRT_CHUNK_PRIO 1     // k_step_merged_chunks: the blocks whose waves share a SIMD take the four issue priorities in turn, pass after pass (path_common.h chunk_priority; C2 43.03 -> 38.01 ms, profiles/r12_c2_bench.json); 0: the oldest wave first, the former schedule
+#endif
 #ifndef XRT_SLOT_INTERLEAVE
 #define XRT_SLOT_INTERLEAVE 1    // merged renders interleave pixels across slots (slot_map.h; C2 51.6 -> 45.6 ms): one-level shards of at least XRT_SLOT_INTERLEAVE_MIN slots, two-level ones that start in whole waves (XRT_BVH_LIVE64); 0: only under XRT_FLAG_INTERLEAVE
 #endif
