@@ -421,6 +421,60 @@ int  xrt_render_var(xrt_ctx* ctx, const xrt_render_params* p, float* rgb_out, fl
 int  xrt_render_var_device(xrt_ctx* ctx, const xrt_render_params* p, float* d_rgb_out, float* d_variance_out,
                            void* hip_stream, xrt_stats* st);
 
+/* ---- progressive rendering: add samples to a frame --------------------------------------- */
+/* A session renders a frame in passes: begin seeds the pixels' streams, every add renders spp more
+ * samples of each pixel from where its stream stands, and frame gives the mean of the samples so far.
+ * A pixel's samples are one sequential mt19937 stream, so passes of n1, n2, ... samples give, bit for
+ * bit, the frame, the variance plane and the path counters of one xrt_render / xrt_render_var at
+ * n1 + n2 + ... samples: 16 spp on screen, then 64, then 1024 cost 1024 samples, not 1104.
+ *
+ * xrt_progressive_begin checks p exactly as xrt_render does (p->spp is ignored), fixes the slot ->
+ * pixel map and the partitions, seeds every slot and zeroes a context-owned accumulator; it renders
+ * nothing.  options: XRT_PROGRESSIVE_VARIANCE also sums the luminance moments of xrt_render_var.
+ *   Schedule: the one xrt_render chooses for p->flags | XRT_FLAG_NO_SPEC | XRT_FLAG_NO_PIXEL; with the
+ *   variance option the one xrt_render_var chooses under XRT_FLAG_VAR_FUSED for the same flags.  The
+ *   pixels no camera ray can hit are traced like the others (no retirement before the path loop).
+ *   Speculative sample starts, pixel-parallel chains and that retirement are not part of a session
+ *   yet: their kernels keep no resumable state per slot.
+ *   Refusals: everything xrt_render refuses, the same way; XRT_ERR_UNSUPPORTED for WhittedIntegrator
+ *   (its kernels never write a stream position back), for XRT_FLAG_ACCUMULATE and for a multi-device
+ *   context — row shards (shard_index / shard_count) work, so one process per GPU can run sessions.
+ *   A second begin replaces the open session.
+ * xrt_progressive_add renders spp more samples of every owned pixel into the accumulator and returns
+ * when they are done.  XRT_ERR_INVALID for spp == 0, without an open session, and when the session's
+ * sample count would overflow uint32_t.  Of *st, samples, segments, shadow_rays, draws, rejected and
+ * stalled are the session's so far — those of one render of spp_done samples at the session's flags —
+ * and schedule, iterations, launches, kernel_ms, wall_ms, the layout fields and rng_twists are this
+ * call's (the kernel that resumes the slots counts under XRT_K_SEED).
+ * xrt_progressive_frame: rgb_out[pixel] = accumulator[pixel] / (float)spp_done for the owned pixels,
+ * +0 elsewhere; variance_out (may be NULL) is xrt_render_var's arithmetic with n = spp_done.  The
+ * accumulator stays undivided: the call can be repeated and does not disturb the session.
+ * XRT_ERR_INVALID before the first add, for variance_out without the variance option and for
+ * variance_out at spp_done < 2.  Afterwards the context's last framebuffer — what xrt_tonemap and the
+ * filters read for a NULL colour — is this frame.  The device entry point orders itself as
+ * xrt_render_var_device does.
+ * A session ends with xrt_progressive_end, with xrt_upload_scene, xrt_set_camera, xrt_set_medium*,
+ * xrt_set_delta_lights, with every render entry point (xrt_render*, xrt_render_var*,
+ * xrt_render_aov*) and with xrt_test_chunk_plan: afterwards add and frame return XRT_ERR_INVALID and
+ * query gives active = 0.  xrt_denoise*, xrt_tonemap, xrt_query and xrt_last_error do not end it:
+ * add, frame, denoise, add is the intended loop. */
+enum { XRT_PROGRESSIVE_VARIANCE = 1u };   /* also sum the luminance moments of xrt_render_var */
+typedef struct {
+    uint32_t active;         /* 1 while a session is open on the context */
+    uint32_t spp_done;       /* samples per pixel accumulated so far */
+    uint32_t passes;         /* xrt_progressive_add calls that completed */
+    uint32_t resume_twists;  /* slots whose ring the last add's resume had to twist */
+    uint64_t path_slots;
+} xrt_progressive_state;
+int  xrt_progressive_begin(xrt_ctx* ctx, const xrt_render_params* p, uint32_t options);
+int  xrt_progressive_add(xrt_ctx* ctx, uint32_t spp, xrt_stats* st);
+/* into caller-owned HOST memory */
+int  xrt_progressive_frame(xrt_ctx* ctx, float* rgb_out, float* variance_out);
+/* into DEVICE pointers on this context's GPU */
+int  xrt_progressive_frame_device(xrt_ctx* ctx, float* d_rgb_out, float* d_variance_out, void* hip_stream);
+int  xrt_progressive_query(const xrt_ctx* ctx, xrt_progressive_state* out);
+int  xrt_progressive_end(xrt_ctx* ctx);
+
 /* ---- first-hit guide buffers (AOVs) --------------------------------------------------- */
 /* Per-pixel guide planes for a denoiser or compositor, taken through the render's own camera
  * rays: sample k of pixel (row i, col j) takes words 2k, 2k + 1 of the pixel's stream (seed

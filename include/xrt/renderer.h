@@ -82,6 +82,21 @@ public:
     // of the wavefront (XRT_FLAG_VAR_FUSED); the same frame and plane, sooner.
     void renderVariance(const Scene& scene, Sampler::SamplerType st, Image& image, std::vector<float>& variance,
                         bool fused = false) const;
+    // A frame in passes (xrt.h, xrt_progressive_*): beginProgressive seeds a session for `scene` at
+    // `image`'s size (the image is not written, n_samples not consulted), every addSamples(n) renders n
+    // more samples of each pixel, and progressiveFrame replaces `image` with the mean of the
+    // samplesDone() samples so far — bit for bit render() over a zero Image at that many samples.
+    // variance = true also sums the luminance moments, so progressiveFrame can fill `variance` as
+    // renderVariance does (from 2 samples on).  The session runs the schedule of render() without
+    // speculative sample starts and pixel-parallel chains; WhittedIntegrator and a multi-GPU renderer
+    // are refused.  Any other render, renderGuides or a new scene ends it; the filters do not.
+    // lastStats() after addSamples: path counters of the session so far, timings of that pass.
+    // Errors as render() reports them.
+    void beginProgressive(const Scene& scene, Sampler::SamplerType st, const Image& image, bool variance = false) const;
+    void addSamples(uint32_t n) const;
+    void progressiveFrame(Image& image, std::vector<float>* variance = nullptr) const;
+    uint32_t samplesDone() const;   // 0 without an open session
+    void endProgressive() const;
     // The guide buffers of the frame render() would make of `scene` with this camera and
     // n_samples (the integrator is not consulted); errors as render() reports them.
     void renderGuides(const Scene& scene, GuideImages& guides) const;

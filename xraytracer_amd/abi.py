@@ -164,6 +164,12 @@ class XrtHit(C.Structure):
                 ("dpdu", C.c_float * 3), ("dpdv", C.c_float * 3), ("barycentric", C.c_float * 2)]
 
 
+class XrtProgressiveState(C.Structure):
+    _fields_ = [("active", C.c_uint32), ("spp_done", C.c_uint32), ("passes", C.c_uint32),
+                ("resume_twists", C.c_uint32), ("path_slots", C.c_uint64)]
+
+
+XRT_PROGRESSIVE_VARIANCE = 1
 XRT_QUERY_INTERSECT, XRT_QUERY_OCCLUDED = 0, 1
 XRT_DENSITY_CORNERS, XRT_DENSITY_ROWS, XRT_DENSITY_BRICKS = 0, 1, 2   # xrt_test_density's layout
 DENSITY_LAYOUTS = ("corners", "rows", "bricks")
@@ -189,6 +195,12 @@ SIGNATURES = {
     "xrt_render_var": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), f32p, f32p, C.POINTER(XrtStats)]),
     "xrt_render_var_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(XrtStats)]),
+    "xrt_progressive_begin": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.c_uint32]),
+    "xrt_progressive_add": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(XrtStats)]),
+    "xrt_progressive_frame": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "xrt_progressive_frame_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "xrt_progressive_query": (C.c_int, [C.c_void_p, C.POINTER(XrtProgressiveState)]),
+    "xrt_progressive_end": (C.c_int, [C.c_void_p]),
     "xrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.POINTER(XrtStats)]),
     "xrt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(XrtRenderParams), C.POINTER(XrtAovBuffers), C.c_void_p,
                                         C.POINTER(XrtStats)]),

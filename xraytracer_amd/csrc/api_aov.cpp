@@ -57,6 +57,7 @@ static int aov_one(xrt_ctx* c, const xrt_render_params* p, const xrt_aov_buffers
                    hipStream_t wait_stream) {
     const auto t_start = std::chrono::steady_clock::now();
     if (!c->has_scene || !c->has_camera) return set_err(c, XRT_ERR_STATE, "upload a scene and set a camera first");
+    end_progressive(c);   // k_seed below resets the slots
     int rc = order_after(c, wait, wait_stream, false);
     if (rc) return rc;
     const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;

@@ -114,6 +114,7 @@ void xrt_destroy(xrt_ctx* c) {
     free_buf(c->brick_table), free_buf(c->brick_data), free_buf(c->corners), free_buf(c->camlist);
     free_buf(c->dlights), free_buf(c->obj_albedo), free_buf(c->aov), free_buf(c->denoise);
     free_buf(c->mom), free_buf(c->var), free_buf(c->chunks);
+    free_buf(c->acc);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (auto& slot : c->poll_ev)
         for (hipEvent_t e : slot)

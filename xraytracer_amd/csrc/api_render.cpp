@@ -78,6 +78,8 @@ bool cdiv_exact(xrt_ctx*, float d) {
     return ok;
 }
 
+}  // namespace
+
 int check_render(xrt_ctx* c, const xrt_render_params* p) {
     if (!c || !p) return XRT_ERR_INVALID;
     if (!c->has_scene || !c->has_camera) return set_err(c, XRT_ERR_STATE, "upload a scene and set a camera first");
@@ -102,6 +104,8 @@ int check_render(xrt_ctx* c, const xrt_render_params* p) {
     if (p->visits_per_launch > 128) return set_err(c, XRT_ERR_INVALID, "visits_per_launch must be 0..128");
     return XRT_OK;
 }
+
+namespace {
 
 // what a variance render refuses beyond check_render
 int check_render_var(xrt_ctx* c, const xrt_render_params* p) {
@@ -180,7 +184,7 @@ KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* f
     P.raspect = 1.0f / P.aspect;
     P.cdiv = (cdiv_exact(c, P.fw) ? 1u : 0u) | (cdiv_exact(c, P.fh) ? 2u : 0u) | (cdiv_exact(c, P.aspect) ? 4u : 0u);
     P.shard_index = p->shard_index, P.shard_count = p->shard_count, P.n_slots = (uint32_t)n;
-    P.spw_req = p->slots_per_wave, P.rflags = p->flags;
+    P.spw_req = p->slots_per_wave, P.rflags = p->flags & ~kRflagSession;   // the bit is a session's to set (progressive_add)
     // two-level traces: the BVH walk takes four lanes per queued ray (k_trace_deep4q, every
     // size: its lanes keep their own best hits) unless the caller asks for one
     const char* dq = exp_env("XRT_DEEP_QUAD");
@@ -212,42 +216,9 @@ void LaunchTimer::read_out() {
     }
 }
 
-namespace {
-
-// The schedule of one render, decided once (plan_render) before anything is launched: the
-// loops, the launchers' arguments and xrt_stats all read it from here.
-struct RenderPlan {
-    int schedule;       // XRT_SCHED_*
-    bool volumetric;    // VPT / VPT-NEE: unbounded walks
-    // pixel: one k_pixel launch between k_seed and k_finish, no live lists, no refill, no
-    // loop (fused and merged are then only what sized the partitions).  Otherwise fused: the
-    // k_step loop (else k_shade + k_trace); merged: its k_step_merged form; two_level: that
-    // kernel with the wave's own BVH walk; step_tri: k_step_tri in place of k_step; spec:
-    // k_step_spec in the merged schedule's group layouts, which needs the camera lists.
-    // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it, or
-    // (whitted_bvh) k_whitted_bvh for a scene beyond LDS under XRT_FLAG_WHITTED_BVH
-    // elide: GI in the merged schedule over at most 64 triangles — k_camlist runs right after the
-    // seeding refill, with or without speculative launches, and finishes the pixels no camera
-    // ray can hit (spec.hip)
-    bool pixel, fused, merged, two_level, step_tri, spec, camlist, elide, whitted, whitted_bvh;
-    uint32_t n_part, part_cap;                     // live-list partitions
-    uint32_t groups;                               // partition groups of the merged schedule's full-wave launches (1: none)
-    uint32_t slot_mul;                             // the slot -> pixel map (slot_map.h): 0 row-major, else interleaved
-    uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
-    uint64_t poll_every, ahead;                    // LivePoll cadence
-    uint64_t cap_iters;                            // loop iterations at most
-    // the whole-wave phase in block-owned chunks (step_chunks.h): passes per block per launch (0: the
-    // grouped schedule from the first round on) and the chunks per class its buffers hold
-    uint32_t chunk_passes, chunk_class_cap;
-    bool chunk_forced;   // by XRT_FLAG_CHUNKS: the phase runs however many chunks the build leaves (build_chunks)
-    // a variance render (xrt_render_var): the slots' {s1, s2} records, which select the moments
-    // builds of k_shade / k_whitted / k_whitted_bvh and, under XRT_FLAG_VAR_FUSED, of k_step /
-    // k_step_tri / k_step_merged; null for a plain render
-    float2* mom;
-};
-
 static_assert(XRT_STEP_GROUPS >= 1 && XRT_STEP_GROUPS <= (int)kMaxStepGroups, "XRT_STEP_GROUPS: 1..3");
 
+// The schedule of one render (RenderPlan, ctx.h), decided once before anything is launched
 RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom) {
     RenderPlan R{};
     R.mom = mom;
@@ -362,6 +333,8 @@ RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom
     return R;
 }
 
+namespace {
+
 // Asynchronous termination polling.  Every `every` loop iterations the live counters that
 // iteration wrote are copied into one of the context's 8 pinned slots, with an event behind
 // the copy.  Polls are retired in order: without blocking once their event has fired, by
@@ -426,6 +399,8 @@ struct LivePoll {
     }
 };
 
+}  // namespace
+
 // k_seed, then the slots' first samples: k_pixel renders them outright; every other schedule
 // twists each slot's ring (the refill k_seed requested).  Last, the device copy of the
 // parameters for the kernels that read them from memory.
@@ -453,6 +428,8 @@ int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveList
     HIPCHK(c, hipMemcpyAsync(c->kparams.p, &P, sizeof(KParams), hipMemcpyHostToDevice, c->stream));
     return XRT_OK;
 }
+
+namespace {
 
 // The fused schedules' loop: one step launch per iteration over three rotating counter
 // arrays — round i reads counts(i % 3), appends to counts((i + 1) % 3) and clears
@@ -510,6 +487,8 @@ class StepGroupStreams {
     bool forked_ = false;
 };
 
+}  // namespace
+
 // The chunk buffer of a render whose plan has the chunk phase (launch.h ChunkBufs), and the chunks
 // themselves from the seeded lists: timed with the seeding.  The host then reads the header back (one
 // wait for the seeding per frame): the chunks that hold a slot, and the grid of the phase's launches
@@ -535,6 +514,8 @@ int build_chunks(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLi
     if (!R.chunk_forced && max_nx > kChunkClassBlocks) B.blocks = 0;
     return XRT_OK;
 }
+
+namespace {
 
 // The whole-wave phase in block-owned chunks, ahead of run_fused's loop and counted as its first
 // iterations: launch `it` adds the live slots it leaves to counts((it + 1) % 3) and clears
@@ -652,6 +633,8 @@ int run_wavefront(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveL
     return XRT_OK;
 }
 
+}  // namespace
+
 // the device's stats words into xrt_stats (and the counters of experiment builds to stderr)
 int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
     unsigned long long hs[48] = {0};
@@ -673,7 +656,55 @@ int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S) {
     return XRT_OK;
 }
 
-}  // namespace
+// the plan's share of the parameters: partitions, refill threshold and slot map, the live lists and the
+// request list behind them, the two-level queues and, where the plan builds them, the camera lists
+int bind_plan(xrt_ctx* c, KParams& P, const RenderPlan& R, LiveLists& L) {
+    P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep, P.slot_mul = R.slot_mul;
+    const size_t lcap = (size_t)P.n_part * P.part_cap;
+    L = LiveLists{{as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap}, as<uint32_t>(c->counts)};
+    P.req = as<uint32_t>(c->lists) + 2 * lcap;
+    int rc;
+    if ((rc = setup_deep(c, P))) return rc;
+    if (R.camlist) {   // the pixels' camera-ray triangle lists: k_step_spec's candidates
+        if ((rc = ensure(c, c->camlist, (size_t)P.n_slots * sizeof(uint4)))) return rc;
+        P.camlist = as<uint4>(c->camlist);
+    }
+    return XRT_OK;
+}
+
+// the path work of a seeded (or resumed) render: the plan's loop until a poll finds no live slot or the
+// iteration cap is reached; a pixel-parallel plan has none.  it: the iterations run; done: a poll saw
+// the lists empty (else check_drained, once the stream is synchronised)
+int run_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, const ChunkBufs& CB, LaunchTimer& T,
+              uint64_t& it, bool& done) {
+    LivePoll poll{c, P.n_part, R.poll_every, R.ahead, R.merged && !P.spw_req, P.n_slots, P.part_cap};
+    it = 0;
+    int rc = XRT_OK;
+    if (!R.pixel) rc = R.fused ? run_fused(c, P, R, L, CB, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it);
+    done = R.pixel || poll.done;
+    return rc;
+}
+
+// the iteration cap was reached without observing an empty list: verify
+int check_drained(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, uint64_t it) {
+    uint32_t left[kMaxParts] = {0};
+    HIPCHK(c, hipMemcpy(left, L.counts(R.fused ? it % 3 : it & 1), P.n_part * 4, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < P.n_part; ++k)
+        if (left[k] != 0) return set_err(c, XRT_ERR_HIP, "iteration cap reached with live paths");
+    return XRT_OK;
+}
+
+// what xrt_stats says about the plan and its run
+void plan_stats(const KParams& P, const RenderPlan& R, uint64_t it, xrt_stats& S) {
+    S.iterations = it;
+    S.schedule = (uint64_t)R.schedule;
+    S.partitions = P.n_part;
+    if (R.fused && !R.pixel) S.visits_per_launch = R.step_visits;
+    if (R.merged && !R.pixel) {
+        S.slots_per_wave = step_merged_spw(P, P.n_slots);   // the layout of the first launch (every launch's: layout_launches)
+        S.group_lanes = step_merged_group(P, S.slots_per_wave);
+    }
+}
 
 int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_out, xrt_stats* st, int wait,
                 hipStream_t wait_stream, float* d_var, ChunkProbe* probe) {
@@ -696,6 +727,7 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
         }
         p = &forced;
     }
+    end_progressive(c);   // the slots are seeded anew
     if ((rc = order_after(c, wait, wait_stream, false))) return rc;
     const size_t n = (size_t)shard_rows(p->height, p->shard_index, p->shard_count) * p->width;
     const size_t npix = (size_t)p->width * p->height;
@@ -722,15 +754,8 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
         probe->passes = R.chunk_passes;
         if (!R.chunk_passes) return XRT_OK;
     }
-    P.n_part = R.n_part, P.part_cap = R.part_cap, P.rng_keep = R.rng_keep, P.slot_mul = R.slot_mul;
-    const size_t lcap = (size_t)P.n_part * P.part_cap;
-    const LiveLists L{{as<uint32_t>(c->lists), as<uint32_t>(c->lists) + lcap}, as<uint32_t>(c->counts)};
-    P.req = as<uint32_t>(c->lists) + 2 * lcap;
-    if ((rc = setup_deep(c, P))) return rc;
-    if (R.camlist) {   // the pixels' camera-ray triangle lists: k_step_spec's candidates
-        if ((rc = ensure(c, c->camlist, n * sizeof(uint4)))) return rc;
-        P.camlist = as<uint4>(c->camlist);
-    }
+    LiveLists L{};
+    if ((rc = bind_plan(c, P, R, L))) return rc;
     xrt_stats S{};
     S.path_slots = n;
     S.samples = (uint64_t)n * p->spp;
@@ -759,10 +784,9 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
     }
 
     // run, finish
-    LivePoll poll{c, P.n_part, R.poll_every, R.ahead, R.merged && !P.spw_req, n, P.part_cap};
     uint64_t it = 0;
-    if (!R.pixel && (rc = R.fused ? run_fused(c, P, R, L, CB, T, poll, it) : run_wavefront(c, P, R, L, T, poll, it)))
-        return rc;
+    bool done = false;
+    if ((rc = run_paths(c, P, R, L, CB, T, it, done))) return rc;
     HIPCHK(c, T.launch(XRT_K_FINISH, [&] {   // a variance render's plane counts as part of the finish
         const hipError_t e = launch_finish(P, c->stream);
         return e != hipSuccess || !R.mom ? e : launch_finish_var(P, R.mom, d_var, c->stream);
@@ -771,24 +795,11 @@ int render_impl(xrt_ctx* c, const xrt_render_params* p, float* d_out, float* h_o
 #if XRT_PHASE_CLOCK
     HIPCHK(c, wave_clock_dump(exp_env("XRT_WAVE_CLOCK_OUT"), c->stream));
 #endif
-    if (!R.pixel && !poll.done) {
-        // the iteration cap was reached without observing an empty list: verify
-        uint32_t left[kMaxParts] = {0};
-        HIPCHK(c, hipMemcpy(left, L.counts(R.fused ? it % 3 : it & 1), P.n_part * 4, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < P.n_part; ++k)
-            if (left[k] != 0) return set_err(c, XRT_ERR_HIP, "iteration cap reached with live paths");
-    }
+    if (!done && (rc = check_drained(c, P, R, L, it))) return rc;
 
     // stats
     if ((rc = read_stats(c, P, S))) return rc;
-    S.iterations = it;
-    S.schedule = (uint64_t)R.schedule;
-    S.partitions = P.n_part;
-    if (R.fused && !R.pixel) S.visits_per_launch = R.step_visits;
-    if (R.merged && !R.pixel) {
-        S.slots_per_wave = step_merged_spw(P, n);   // the layout of the first launch (every launch's: layout_launches)
-        S.group_lanes = step_merged_group(P, S.slots_per_wave);
-    }
+    plan_stats(P, R, it, S);
     T.read_out();
     if (h_out) HIPCHK(c, hipMemcpy(h_out, fb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     S.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();

@@ -591,22 +591,27 @@ int set_medium_bricks_one(xrt_ctx* c, const xrt_medium_desc* m, const xrt_brick_
 extern "C" {
 
 int xrt_upload_scene(xrt_ctx* c, const xrt_scene_desc* s) {
+    end_progressive(c);   // an open progressive session renders what was set before
     return for_each_device(c, "xrt_upload_scene", [&](xrt_ctx* d) { return upload_scene_one(d, s); });
 }
 
 int xrt_set_camera(xrt_ctx* c, const float c2w[16], float scale, float aspect) {
+    end_progressive(c);   // an open progressive session renders what was set before
     return for_each_device(c, "xrt_set_camera", [&](xrt_ctx* d) { return set_camera_one(d, c2w, scale, aspect); });
 }
 
 int xrt_set_delta_lights(xrt_ctx* c, const xrt_delta_light* lights, uint32_t n) {
+    end_progressive(c);   // an open progressive session renders what was set before
     return for_each_device(c, "xrt_set_delta_lights", [&](xrt_ctx* d) { return set_delta_lights_one(d, lights, n); });
 }
 
 int xrt_set_medium(xrt_ctx* c, const xrt_medium_desc* m) {
+    end_progressive(c);   // an open progressive session renders what was set before
     return for_each_device(c, "xrt_set_medium", [&](xrt_ctx* d) { return set_medium_one(d, m); });
 }
 
 int xrt_set_medium_bricks(xrt_ctx* c, const xrt_medium_desc* m, const xrt_brick_grid* g) {
+    end_progressive(c);   // an open progressive session renders what was set before
     return for_each_device(c, "xrt_set_medium_bricks", [&](xrt_ctx* d) { return set_medium_bricks_one(d, m, g); });
 }
 

@@ -21,6 +21,20 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
 };
+
+// An open progressive session (xrt_progressive_*, api_progressive.cpp).  Between its passes the slots'
+// streams (ring, rng_c, rng_g), their counters (c_*) and moments records (mom) and the accumulator are
+// the session's state: whatever seeds the slots anew or changes what they render ends it
+// (end_progressive).
+struct ProgressiveSession {
+    bool active = false;
+    xrt_render_params p{};     // as given to begin, with the session's schedule flags (spp: unused)
+    bool variance = false;     // XRT_PROGRESSIVE_VARIANCE
+    size_t n = 0;              // the shard's slots
+    uint32_t spp_done = 0, passes = 0, resume_twists = 0;
+    uint64_t twists = 0;       // ring twists of the slots so far (xrt_stats::rng_twists is per add)
+};
+
 }  // namespace xrt
 
 struct xrt_ctx {
@@ -73,6 +87,9 @@ struct xrt_ctx {
     // xrt_denoise, xrt_denoise_var: the per-pixel records (two colour buffers, normal, albedo: 16 B
     // each), then for the host entry points the staged input planes and the output planes
     xrt::DevBuf denoise;
+    // xrt_progressive_*: the open session and its accumulator [H][W][3], the pixels' undivided sums
+    xrt::ProgressiveSession prog;
+    xrt::DevBuf acc;
 };
 
 namespace xrt {
@@ -179,6 +196,54 @@ struct LiveLists {
 int setup_deep(xrt_ctx* c, KParams& P);   // the two-level trace queues (KParams::deep)
 int grow_slots(xrt_ctx* c, size_t n);
 KParams render_params(xrt_ctx* c, const xrt_render_params* p, size_t n, float* fb);
+
+// The pieces of render_impl's sequence, which a progressive session runs in an order of its own
+// (api_progressive.cpp: seeding in begin; resume, run and finish in every add).
+int check_render(xrt_ctx* c, const xrt_render_params* p);   // what every render entry point refuses
+// The schedule of one render, decided once (plan_render) before anything is launched: the
+// loops, the launchers' arguments and xrt_stats all read it from here.
+struct RenderPlan {
+    int schedule;       // XRT_SCHED_*
+    bool volumetric;    // VPT / VPT-NEE: unbounded walks
+    // pixel: one k_pixel launch between k_seed and k_finish, no live lists, no refill, no
+    // loop (fused and merged are then only what sized the partitions).  Otherwise fused: the
+    // k_step loop (else k_shade + k_trace); merged: its k_step_merged form; two_level: that
+    // kernel with the wave's own BVH walk; step_tri: k_step_tri in place of k_step; spec:
+    // k_step_spec in the merged schedule's group layouts, which needs the camera lists.
+    // whitted: WhittedIntegrator — pixel's shape (one launch, no lists), k_whitted in it, or
+    // (whitted_bvh) k_whitted_bvh for a scene beyond LDS under XRT_FLAG_WHITTED_BVH
+    // elide: GI in the merged schedule over at most 64 triangles — k_camlist runs right after the
+    // seeding refill, with or without speculative launches, and finishes the pixels no camera
+    // ray can hit (spec.hip)
+    bool pixel, fused, merged, two_level, step_tri, spec, camlist, elide, whitted, whitted_bvh;
+    uint32_t n_part, part_cap;                     // live-list partitions
+    uint32_t groups;                               // partition groups of the merged schedule's full-wave launches (1: none)
+    uint32_t slot_mul;                             // the slot -> pixel map (slot_map.h): 0 row-major, else interleaved
+    uint32_t step_visits, spec_visits, rng_keep;   // segments per slot per launch; ring words a launch may need
+    uint64_t poll_every, ahead;                    // LivePoll cadence
+    uint64_t cap_iters;                            // loop iterations at most
+    // the whole-wave phase in block-owned chunks (step_chunks.h): passes per block per launch (0: the
+    // grouped schedule from the first round on) and the chunks per class its buffers hold
+    uint32_t chunk_passes, chunk_class_cap;
+    bool chunk_forced;   // by XRT_FLAG_CHUNKS: the phase runs however many chunks the build leaves (build_chunks)
+    // a variance render (xrt_render_var): the slots' {s1, s2} records, which select the moments
+    // builds of k_shade / k_whitted / k_whitted_bvh and, under XRT_FLAG_VAR_FUSED, of k_step /
+    // k_step_tri / k_step_merged; null for a plain render
+    float2* mom;
+};
+RenderPlan plan_render(const KParams& P, const xrt_render_params* p, float2* mom);
+int bind_plan(xrt_ctx* c, KParams& P, const RenderPlan& R, LiveLists& L);
+int seed_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T);
+int build_chunks(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, LaunchTimer& T, ChunkBufs& B);
+int run_paths(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, const ChunkBufs& CB, LaunchTimer& T,
+              uint64_t& it, bool& done);
+int check_drained(xrt_ctx* c, const KParams& P, const RenderPlan& R, const LiveLists& L, uint64_t it);
+int read_stats(xrt_ctx* c, const KParams& P, xrt_stats& S);
+void plan_stats(const KParams& P, const RenderPlan& R, uint64_t it, xrt_stats& S);
+// what seeds the slots anew, or changes the scene, camera, medium or lights they render, ends the session
+inline void end_progressive(xrt_ctx* c) {
+    if (c) c->prog.active = false;
+}
 // wait, wait_stream: order_after's.  d_var: a variance render (xrt_render_var) — the device plane
 // [height][width] that gets the variance of each pixel's mean luminance; null: a plain render
 // probe: xrt_test_chunk_plan — the plan's chunk phase and, when it has one, the chunks built after

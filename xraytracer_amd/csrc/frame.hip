@@ -65,49 +65,26 @@ __global__ __launch_bounds__(kBlock) void k_seed(KParams P, uint32_t* list, uint
 // ================================================================== k_finish ====
 // Image::operator/=(Vec3f(n_samples)) over this shard's pixels + counter reduction.
 __global__ __launch_bounds__(kBlock) void k_finish(KParams P) {
-    __shared__ unsigned long long red[6][kBlock / 64];
-    unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
-    const float n = (float)P.spp;
+    SlotCounters cnt;
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < P.n_slots; s += gridDim.x * kBlock) {
         const SlotPixel pix = slot_pixel(P, s);
         const uint32_t col = pix.col, row = pix.row;
         float* px = P.fb + 3 * ((size_t)col + (size_t)P.width * row);
-        px[0] = px[0] / n, px[1] = px[1] / n, px[2] = px[2] / n;
-        a[0] += P.c_seg[s];
-        a[1] += P.c_shadow[s];
-        a[2] += P.rng_c[s] - kMT;
-        a[3] += P.c_rej[s];
-        a[4] += P.c_stall[s];
-        a[5] += P.rng_g[s] / kMT - 1u;   // twists: k_seed leaves g = kMT, every twist adds kMT
+        const v3 mean = frame_mean(mk(px[0], px[1], px[2]), P.spp);
+        px[0] = mean.x, px[1] = mean.y, px[2] = mean.z;
+        cnt.add(P, s);
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        unsigned long long v = a[q];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        if (lane == 0) red[q][wv] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {   // stats[0..4], twists to stats[7] (5, 6: experiment counters)
-        unsigned long long v = 0;
-        for (int w = 0; w < kBlock / 64; ++w) v += red[threadIdx.x][w];
-        atomicAdd(P.stats + (threadIdx.x < 5 ? threadIdx.x : 7u), v);
-    }
+    cnt.reduce(P);
 }
 
 // ============================================================== k_finish_var ====
 // A variance render's plane (xrt_render_var, include/xrt.h) from the slots' {s1, s2} records: the
 // variance of the pixel's mean luminance, one rounding per operation.
 __global__ __launch_bounds__(kBlock) void k_finish_var(KParams P, const float2* __restrict__ mom, float* __restrict__ var) {
-    const float n = (float)P.spp;
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < P.n_slots; s += gridDim.x * kBlock) {
         const SlotPixel pix = slot_pixel(P, s);
         const uint32_t col = pix.col, row = pix.row;
-        const float2 m = mom[s];
-        const float mean = m.x / n;
-        float v = m.y / n - mean * mean;
-        v = v > 0.0f ? v : 0.0f;
-        var[(size_t)col + (size_t)P.width * row] = v / (float)(P.spp - 1u);
+        var[(size_t)col + (size_t)P.width * row] = frame_variance(mom[s], P.spp);
     }
 }
 

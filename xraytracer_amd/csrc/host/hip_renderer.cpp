@@ -161,6 +161,35 @@ void HipRenderer::renderVariance(const Scene& scene, Sampler::SamplerType, Image
     if (rc != XRT_OK) fail(rc, std::string("xrt_render_var: ") + xrt_last_error(m_ctx));
 }
 
+void HipRenderer::beginProgressive(const Scene& scene, Sampler::SamplerType, const Image& image, bool variance) const {
+    xrt_render_params p;
+    if (!renderInputs(scene, image, p)) return;
+    const int rc = xrt_progressive_begin(m_ctx, &p, variance ? XRT_PROGRESSIVE_VARIANCE : 0u);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_progressive_begin: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::addSamples(uint32_t n) const {
+    if (context() != XRT_OK) return;
+    const int rc = xrt_progressive_add(m_ctx, n, &m_stats);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_progressive_add: ") + xrt_last_error(m_ctx));
+}
+
+void HipRenderer::progressiveFrame(Image& image, std::vector<float>* variance) const {
+    if (context() != XRT_OK) return;
+    if (variance) variance->assign((size_t)image.getWidth() * image.getHeight(), 0.0f);
+    const int rc = xrt_progressive_frame(m_ctx, image.data(), variance ? variance->data() : nullptr);
+    if (rc != XRT_OK) fail(rc, std::string("xrt_progressive_frame: ") + xrt_last_error(m_ctx));
+}
+
+uint32_t HipRenderer::samplesDone() const {
+    xrt_progressive_state s{};
+    return m_ctx && xrt_progressive_query(m_ctx, &s) == XRT_OK ? s.spp_done : 0u;
+}
+
+void HipRenderer::endProgressive() const {
+    if (m_ctx) (void)xrt_progressive_end(m_ctx);
+}
+
 bool HipRenderer::renderInputs(const Scene& scene, const Image& image, xrt_render_params& p) const {
     auto fail = [&](int rc, const char* what) {
         m_status = rc;

@@ -76,6 +76,18 @@ hipError_t launch_test_slot_map(const KParams& P, uint32_t* out, hipStream_t st)
 // Image::gammaCorrection + writePPM quantisation of n floats into n bytes
 hipError_t launch_tonemap(const float* rgb, uint32_t n, float inv_gamma, uint8_t* out, hipStream_t st);
 
+// ---------------------------------------------------------------- progressive.hip ----
+// A progressive session's pass (xrt_progressive_add) between launch_resume and launch_progress_finish.
+// launch_resume takes launch_seed's arguments and leaves its lists and counters (nothing requested),
+// but of a slot only restarts the sample loop: streams, counters and moments stay, and a ring with fewer
+// than P.rng_keep words ahead is twisted (counted in stats[kStatsResume])
+hipError_t launch_resume(const KParams& P, uint32_t* list, uint32_t* count, uint32_t* count_other, uint32_t* req_count,
+                         hipStream_t st);
+hipError_t launch_progress_finish(const KParams& P, hipStream_t st);   // launch_finish's counters, no division
+// rgb [height][width][3] = P.fb / P.spp and, with mom and var, var [height][width] as launch_finish_var's,
+// the shard's pixels only
+hipError_t launch_progress_frame(const KParams& P, float* rgb, const float2* mom, float* var, hipStream_t st);
+
 // ---------------------------------------------------------------------- trace.hip ----
 // zero_deep: clear the two-level trace's queue counters first (false when the k_shade that
 // precedes this trace in the render loop has cleared them)

@@ -792,6 +792,55 @@ __device__ __forceinline__ bool radiance_invalid(v3 r) {
 // the weights xrt_denoise_var reads its colour stop with, in its order of operations)
 __device__ __forceinline__ float luminance(v3 r) { return (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z; }
 
+// What ends a frame, each formula once: k_finish / k_finish_var (frame.hip) apply them in place after a
+// one-shot render, k_progress_frame (progressive.hip) out of place after any pass of a session.
+// frame_mean: Image::operator/=(Vec3f(n_samples)) on one pixel's running sum.
+__device__ __forceinline__ v3 frame_mean(v3 sum, uint32_t spp) {
+    const float n = (float)spp;
+    return mk(sum.x / n, sum.y / n, sum.z / n);
+}
+// frame_variance: the variance of the pixel's mean luminance from its {s1, s2} record (include/xrt.h,
+// xrt_render_var's last five operations), one rounding per operation
+__device__ __forceinline__ float frame_variance(float2 m, uint32_t spp) {
+    const float n = (float)spp;
+    const float mean = m.x / n;
+    float v = m.y / n - mean * mean;
+    v = v > 0.0f ? v : 0.0f;
+    return v / (float)(spp - 1u);
+}
+
+// The slots' path counters into KParams::stats (k_finish, k_progress_finish): each thread adds its slots,
+// then reduce() — by every thread of the block — sums the block's and adds them to stats[0..4] and,
+// the twists, to stats[7] (5, 6: experiment counters).  The counters are absolute stream positions and
+// running counts, so after the passes of a session they are what one render of all the samples leaves.
+struct SlotCounters {
+    unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
+    __device__ __forceinline__ void add(const KParams& P, uint32_t s) {
+        a[0] += P.c_seg[s];
+        a[1] += P.c_shadow[s];
+        a[2] += P.rng_c[s] - kMT;
+        a[3] += P.c_rej[s];
+        a[4] += P.c_stall[s];
+        a[5] += P.rng_g[s] / kMT - 1u;   // twists: k_seed leaves g = kMT, every twist adds kMT
+    }
+    __device__ __forceinline__ void reduce(const KParams& P) {
+        __shared__ unsigned long long red[6][kBlock / 64];
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            unsigned long long v = a[q];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+            if (lane == 0) red[q][wv] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            unsigned long long v = 0;
+            for (int w = 0; w < kBlock / 64; ++w) v += red[threadIdx.x][w];
+            atomicAdd(P.stats + (threadIdx.x < 5 ? threadIdx.x : 7u), v);
+        }
+    }
+};
+
 // Russian roulette past depth 0 (Src/integrator.h:148-155, 224-231, 432-439, 508-515): false =
 // the path ends here; else throughput / Vec3f(p).  (k_shade and k_step hold it open-coded, see
 // there; k_step's volumetric integrators with the quotient through div3s: one division for an

@@ -328,7 +328,8 @@ __global__ __launch_bounds__(kBlock, XRT_SHADE_WAVES) void k_shade(KParams P, co
             }
             if (st & ST_REGEN) {   // very first sample of the slot
                 st &= ~ST_REGEN;
-                if (MOM) mom[s] = make_float2(0.0f, 0.0f);
+                // a progressive session's passes each start here; its records were zeroed once, by begin
+                if (MOM && !(P.rflags & kRflagSession)) mom[s] = make_float2(0.0f, 0.0f);
                 const SlotPixel pix = slot_pixel_rowmajor(P, s);
                 const uint32_t col = pix.col, row = pix.row;
                 const float u = div_w(P, (float)(int)col + rng.next());

@@ -154,6 +154,10 @@ constexpr int kStatsPix = 8;                // KParams::stats words 8..14: k_pix
 constexpr int kStatsWhit = 16;               // KParams::stats words 16..19: k_whitted's counters (xrt_stats whit_*)
 constexpr int kStatsPhase = 40;             // KParams::stats words 40..47: XRT_PHASE_CLOCK builds' phase cycles
 constexpr int kStatsWork = 32;               // KParams::stats word k_pixel counts the pixels taken in
+constexpr int kStatsResume = 20;             // KParams::stats word k_resume counts the slots it twisted in (progressive.hip)
+// KParams::rflags beyond xrt_render_params.flags (no public flag takes the bit): the launch belongs to a
+// progressive session (xrt_progressive_add), whose slots keep their moments records between passes
+constexpr uint32_t kRflagSession = 1u << 31;
 constexpr unsigned kPixLds = 160u * 1024u;   // k_pixel: scene + per-wave stream windows (gfx950: 160 KiB per workgroup)
 
 struct DLight {  // e1/e2/Ng precomputed on the host with the reference constructor's ops
@@ -254,7 +258,7 @@ struct KParams {
     uint32_t n_part, part_cap;   // live-list partitions: n_part (<= kMaxParts) of part_cap slots
     uint32_t rng_keep;           // fused schedule refill threshold (words ahead)
     uint32_t spw_req;            // merged schedule: requested slots per wave (0 = by live count)
-    uint32_t rflags;             // xrt_render_params.flags
+    uint32_t rflags;             // xrt_render_params.flags; bit 31: kRflagSession
     uint32_t lds_max;            // the device's LDS bytes per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock)
     uint4* camlist;              // speculative starts (spec.hip): per slot the pixel's camera-ray triangle list
     // ---- slot state (SoA)

@@ -16,6 +16,62 @@ from . import abi
 from .scenes import SceneBundle
 
 
+class ProgressiveSession:
+    """A frame rendered in passes (xrt_progressive_*): ``add(spp)`` renders spp more samples of every
+    pixel, ``frame()`` is the mean of the samples so far — bit for bit what one render() at spp_done
+    samples gives.  Made by HipRenderer.progressive(); a context manager.  Uploading a scene or any
+    render on the same HipRenderer ends it (add and frame then raise)."""
+
+    def __init__(self, renderer, width, height, variance):
+        self._r, self._lib = renderer, renderer._lib
+        self.width, self.height, self.variance = width, height, bool(variance)
+        self.stats = None   # the last add's xrt_stats: path counters of the session so far, timings of that add
+
+    @property
+    def state(self) -> abi.XrtProgressiveState:
+        s = abi.XrtProgressiveState()
+        self._r._check(self._lib.xrt_progressive_query(self._r.ctx, C.byref(s)), "xrt_progressive_query")
+        return s
+
+    @property
+    def spp_done(self) -> int:
+        return int(self.state.spp_done)
+
+    def add(self, spp: int):
+        st = abi.XrtStats()
+        self._r._check(self._lib.xrt_progressive_add(self._r.ctx, int(spp), C.byref(st)), "xrt_progressive_add")
+        self.stats = self._r.stats = st
+        return st
+
+    def frame(self, variance: bool = None):
+        """(H, W, 3) float32, and in a session with variance=True also the (H, W) variance plane of
+        render_var (which needs spp_done >= 2; variance=False: the frame alone)"""
+        want = self.variance if variance is None else bool(variance)
+        img = np.zeros((self.height, self.width, 3), np.float32)
+        var = np.zeros((self.height, self.width), np.float32) if want else None
+        self._r._check(self._lib.xrt_progressive_frame(self._r.ctx, abi.fptr(img), abi.fptr(var) if want else None),
+                       "xrt_progressive_frame")
+        return (img, var) if want else img
+
+    def frame_device(self, out: int, var: int = None, after_stream=None):
+        """the frame into device memory: out H*W*3 float32, var H*W float32 or None (torch tensor
+        .data_ptr()); after_stream as for render_var_device"""
+        self._r._check(self._lib.xrt_progressive_frame_device(self._r.ctx, C.c_void_p(out or None), C.c_void_p(var or None),
+                                                              C.c_void_p(after_stream or None)),
+                       "xrt_progressive_frame_device")
+
+    def close(self):
+        if self._r is not None and self._r.ctx:
+            self._lib.xrt_progressive_end(self._r.ctx)
+        self._r = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class HipRenderer:
     def __init__(self, spp: int, device: int = 0, devices=None):
         """device: one GPU; devices: a list of GPUs rendered as one (xrt_create_multi —
@@ -131,6 +187,19 @@ class HipRenderer:
         self._check(self._lib.xrt_render(self.ctx, C.byref(p), abi.fptr(img), C.byref(st)), "xrt_render")
         self.stats = st
         return img
+
+    def progressive(self, scene: SceneBundle, width: int, height: int, variance: bool = False, **kw) -> ProgressiveSession:
+        """Open a progressive session (xrt_progressive_begin) and return it: add(spp), frame(),
+        frame_device(), spp_done, state, stats, close().  variance: also sum the luminance moments, so
+        frame() returns (img, var) as render_var does.  self.spp is ignored.  The schedule is render()'s
+        with spec=False and without pixel-parallel chains; WhittedIntegrator, accumulate and a
+        multi-device renderer are refused.  kw: params()'s."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        p = self.params(scene, width, height, **kw)
+        self._check(self._lib.xrt_progressive_begin(self.ctx, C.byref(p), abi.XRT_PROGRESSIVE_VARIANCE if variance else 0),
+                    "xrt_progressive_begin")
+        return ProgressiveSession(self, width, height, variance)
 
     def render_var(self, scene: SceneBundle, width: int, height: int, **kw):
         """The frame and the variance of each pixel's mean luminance (xrt_render_var): ((H, W, 3),
