@@ -772,6 +772,15 @@ int xrt_test_corner_grid_limit(xrt_ctx* ctx, uint64_t max_bytes);
 int xrt_test_hg(xrt_ctx* ctx, float g, const float* wo, const uint32_t* words, uint32_t n, float* wi);
 int xrt_test_wavelength(xrt_ctx* ctx, const float* thr, const float* albedo, const uint32_t* words, uint32_t n,
                         uint32_t* channel, float* pmf);
+/* What the last xrt_upload_scene built for the kernels that walk a hierarchy (csrc/bvh.h), read from
+ * the context; nothing is launched.  out = {nodes of the triangle BVH, stack entries per ray of its
+ * binary walk (tree depth + 1, at most 24), nodes of its 4-wide form, stack entries of that walk
+ * (3 * depth + 1, at most 48; both 0 unless the scene is two-level), 1 if the scene is two-level,
+ * nodes of the threaded sphere BVH, triangles in the triangle BVH (those with a zero edge vector are
+ * left out), bytes per stack entry (2 or 4) of the walk the scene's deep rays take — the 4-wide one
+ * of a two-level scene, else the binary one}; all 0 for a scene without the structure.
+ * XRT_ERR_STATE without an uploaded scene. */
+int xrt_test_bvh_info(xrt_ctx* ctx, int32_t out[8]);
 
 #ifdef __cplusplus
 }

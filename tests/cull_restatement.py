@@ -85,7 +85,7 @@ class Culls:
     tri_lo, tri_hi [T, 3]        padded per-triangle boxes of the BVH's triangles (NaN: not in it)
     tri_in_bvh [T]               the triangle is walked through the BVH
     tri_dropped [T]              ... or left out of it for a zero edge vector
-    sph_lo, sph_hi [S, 3]        padded per-sphere boxes (sphere BVH)
+    sph_lo, sph_hi [S, 3]        padded per-sphere boxes (sphere BVH); s_lo, s_hi: unpadded
     pad_obj, pad_bvh             the margins used
     force_bvh: build the one-level BVH's boxes although the scene is small (what the same triangles
     would get inside a larger scene's BVH with these bounds)."""
@@ -150,6 +150,7 @@ class Culls:
             r = np.abs(sp[:, 3:4])
             lo, hi = (sp[:, :3] - r).astype(F), (sp[:, :3] + r).astype(F)
             self.pad_bvh = pad(lo.min(0), hi.max(0), K_BVH)
+            self.s_lo, self.s_hi = lo, hi          # as build_sphere_bvh hands them to the build
             self.sph_lo, self.sph_hi = (lo - self.pad_bvh).astype(F), (hi + self.pad_bvh).astype(F)
             self.sph_first = np.cumsum([0] + [o.count if o.kind == abi.XRT_OBJ_SPHERE else 0 for o in objs])[:-1]
             self.sphere_bvh = True

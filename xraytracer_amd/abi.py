@@ -248,6 +248,7 @@ SIGNATURES = {
     "xrt_test_corner_grid_limit": (C.c_int, [C.c_void_p, C.c_uint64]),
     "xrt_test_hg": (C.c_int, [C.c_void_p, C.c_float, f32p, u32p, C.c_uint32, f32p]),
     "xrt_test_wavelength": (C.c_int, [C.c_void_p, f32p, f32p, u32p, C.c_uint32, u32p, f32p]),
+    "xrt_test_bvh_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // api_query.cpp — the C ABI of include/xrt.h, what runs on a context's first device beside the
 // renders: ray queries, the tone map and the device self-tests.
+#include "bvh_walk.h"
 #include "ctx.h"
 
 using namespace xrt;
@@ -255,6 +256,19 @@ int xrt_test_wavelength(xrt_ctx* c, const float* thr, const float* albedo, const
     if (e == hipSuccess) e = hipMemcpy(pmf, dp.p, (size_t)n * 12, hipMemcpyDeviceToHost);
     free_buf(dt), free_buf(da), free_buf(dw), free_buf(dc), free_buf(dp);
     return e == hipSuccess ? XRT_OK : hip_err(c, e, "xrt_test_wavelength");
+}
+
+// what upload_scene_one built for the walks of the uploaded scene; reads the context only
+int xrt_test_bvh_info(xrt_ctx* c, int32_t out[8]) {
+    c = first_device(c);
+    if (!c || !out) return XRT_ERR_INVALID;
+    if (!c->has_scene) return set_err(c, XRT_ERR_STATE, "upload a scene first");
+    const KParams& P = c->base;
+    const uint32_t entry = P.two_level ? bvh4_lds(P).entry : bvh_lds(P).entry;
+    out[0] = P.bvh_nodes, out[1] = P.bvh_stack, out[2] = P.bvh4_nodes, out[3] = P.bvh4_stack;
+    out[4] = P.two_level, out[5] = P.n_snode, out[6] = c->bvh_tris;
+    out[7] = P.bvh_nodes > 0 ? (int32_t)entry : 0;
+    return XRT_OK;
 }
 
 }  // extern "C"

@@ -276,6 +276,7 @@ int build_tri_bvh(xrt_ctx* c, const FlatScene& F) {
     P.bvh_node = nullptr, P.bvh_tri = nullptr, P.bvh_stack = 0, P.bvh_nodes = 0;
     P.stri = nullptr, P.sbox = nullptr, P.splane = nullptr, P.n_stri = 0, P.n_sobj = 0, P.two_level = 0;
     P.sstep = nullptr, P.bvh4 = nullptr, P.bvh4_nodes = 0, P.bvh4_stack = 0, P.deep_quad = 0;
+    c->bvh_tris = 0;
     if (!(P.scene_kind == SCN_TRI && !P.small_tri && P.n_tris > 0 && !exp_env("XRT_NO_BVH"))) return XRT_OK;
     const std::vector<f4>& tri = F.tri;
     // two-level split: mesh objects of more than kLargeObjTris triangles go into the BVH,
@@ -342,7 +343,12 @@ int build_tri_bvh(xrt_ctx* c, const FlatScene& F) {
             P.sstep = P.det_bounded ? &c->sstep : nullptr;   // k_trace_2a_coop: ray_tri_nb
         }
     }
-    const BvhBuild B = build_bvh(mn.data(), mx.data(), (uint32_t)nt, kBvhLeafTri, scene.pad(1e-4f), kBvhMaxDepth);
+    // the SAH tree when the walks' stacks hold it (every scene with a reasonably even mesh), else
+    // one with fewer SAH levels: a mesh that spans many octaves of scale lets SAH peel a bin off
+    // per level, and the reference renders it all the same
+    const BvhFit fit = build_bvh_fit(mn.data(), mx.data(), (uint32_t)nt, kBvhLeafTri, scene.pad(1e-4f), kBvhMaxDepth,
+                                     kBvhStack, P.two_level ? kBvh4Stack : 0);
+    const BvhBuild& B = fit.bvh;
     if (B.depth >= kBvhStack) return set_err(c, XRT_ERR_UNSUPPORTED, "BVH deeper than the traversal stack");
     std::vector<f4> btri(3 * nt);
     for (size_t i = 0; i < nt; ++i) {
@@ -356,9 +362,10 @@ int build_tri_bvh(xrt_ctx* c, const FlatScene& F) {
     P.bvh_node = as<f4>(c->bvh_node), P.bvh_tri = as<f4>(c->bvh_tri);
     P.bvh_stack = B.depth + 1;
     P.bvh_nodes = (int)B.nodes.size();
+    c->bvh_tris = (int)nt;
     if (P.two_level) {   // the deep rays walk the 4-wide form
-        int d4 = 0;
-        const std::vector<Bvh4Node> b4 = collapse_bvh4(B, d4);
+        const int d4 = fit.depth4;
+        const std::vector<Bvh4Node>& b4 = fit.bvh4;
         if (3 * d4 + 1 > kBvh4Stack) return set_err(c, XRT_ERR_UNSUPPORTED, "4-wide BVH deeper than the traversal stack");
         if ((rc = upload(c, c->bvh4, b4.data(), b4.size() * sizeof(Bvh4Node)))) return rc;
         P.bvh4 = as<f4>(c->bvh4), P.bvh4_nodes = (int)b4.size(), P.bvh4_stack = 3 * d4 + 1;

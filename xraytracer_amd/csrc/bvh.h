@@ -63,9 +63,31 @@ struct Bvh4Node {
 // `depth`: the deepest node (a traversal pushes at most 3 children per level)
 std::vector<Bvh4Node> collapse_bvh4(const BvhBuild& b, int& depth);
 
-// prim_min / prim_max: n boxes (3 floats each).  Binned SAH, leaves of <= leaf_max
-// primitives, median split below max_depth - 8 levels of headroom; margin pads every box.
+// prim_min / prim_max: n boxes (3 floats each).  Leaves of <= leaf_max primitives; margin pads
+// every box.  Binned SAH splits the nodes at depth < max_depth - kBvhMedianLevels, the median of
+// the centroids along their widest axis the deeper ones (and any node SAH cannot split): SAH may
+// peel one bin off per level, a median split halves the count, so max_depth <= kBvhMedianLevels
+// gives the balanced tree, about log2(n / leaf_max) deep.
+constexpr int kBvhMedianLevels = 24;
 BvhBuild build_bvh(const float* prim_min, const float* prim_max, uint32_t n, uint32_t leaf_max, float margin,
                    int max_depth);
+
+// build_bvh for walks with bounded stacks: a binary walk of `stack` entries takes depth < stack,
+// a 4-wide walk of `stack4` entries 3 * (collapse_bvh4's depth) + 1 <= stack4 (stack4 <= 0: no
+// 4-wide form is needed).  The first build is build_bvh(..., max_depth) itself and is returned
+// when it fits, so a tree that fits is the tree it always was; otherwise the build is repeated
+// with kBvhSahStep fewer SAH levels at a time, down to median splits only.  `fits` is false when
+// even that tree does not fit (2^24 boxes at leaf_max 4 give a median-only depth of 22; more
+// boxes or smaller stacks may fit no tree).
+constexpr int kBvhSahStep = 4;
+struct BvhFit {
+    BvhBuild bvh;
+    std::vector<Bvh4Node> bvh4;   // its 4-wide form and that form's depth, when stack4 > 0
+    int depth4 = 0;
+    int sah_levels = 0;           // the SAH levels of the build returned (max_depth - kBvhMedianLevels: the first)
+    bool fits = false;
+};
+BvhFit build_bvh_fit(const float* prim_min, const float* prim_max, uint32_t n, uint32_t leaf_max, float margin,
+                     int max_depth, int stack, int stack4);
 
 }  // namespace xrt

@@ -48,6 +48,7 @@ struct xrt_ctx {
     xrt::StepObjs step_objs{};   // kernel-argument object records of the merged-trace schedule
     xrt::StepObjs sstep{};       // two-level trace: the small objects' records (KParams::sstep)
     bool has_scene = false, has_camera = false, has_medium = false;
+    int bvh_tris = 0;            // triangles in the triangle BVH's reordered array (xrt_test_bvh_info)
     // WhittedIntegrator: the delta lights (kept across scene uploads), and whether the scene
     // holds a metal / glass object (valid only under Whitted) or a glass one (depth limit)
     xrt::DevBuf dlights;

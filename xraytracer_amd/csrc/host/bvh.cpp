@@ -54,13 +54,15 @@ struct Builder {
                              [axis](const Ref& a, const Ref& b) { return a.c[axis] < b.c[axis]; });
             return mid;
         };
-        if (!(ext > 0.0f) || depth >= max_depth - 24) return median();
+        if (!(ext > 0.0f) || depth >= max_depth - kBvhMedianLevels) return median();
         constexpr int kBins = 16;
         Box bb[kBins];
         uint32_t bc[kBins] = {0};
+        // (compared as a float first: boxes next to +-FLT_MAX give infinite centroids and a NaN here,
+        // which goes to bin 0 like every value below 1)
         auto bin_of = [&](const Ref& r) {
-            int b = (int)((r.c[axis] - cb.mn[axis]) / ext * kBins);
-            return std::min(std::max(b, 0), kBins - 1);
+            const float f = (r.c[axis] - cb.mn[axis]) / ext * kBins;
+            return f >= (float)kBins ? kBins - 1 : (f >= 1.0f ? (int)f : 0);
         };
         for (uint32_t i = lo; i < hi; ++i) {
             const int b = bin_of(refs[i]);
@@ -170,6 +172,22 @@ BvhBuild build_bvh(const float* prim_min, const float* prim_max, uint32_t n, uin
     }
     nodes.swap(out);
     return std::move(B.out);
+}
+
+BvhFit build_bvh_fit(const float* prim_min, const float* prim_max, uint32_t n, uint32_t leaf_max, float margin,
+                     int max_depth, int stack, int stack4) {
+    BvhFit f;
+    f.sah_levels = std::max(0, max_depth - kBvhMedianLevels);
+    while (true) {
+        f.bvh = build_bvh(prim_min, prim_max, n, leaf_max, margin, kBvhMedianLevels + f.sah_levels);
+        f.fits = f.bvh.depth < stack;
+        if (stack4 > 0) {
+            f.bvh4 = collapse_bvh4(f.bvh, f.depth4);
+            f.fits = f.fits && 3 * f.depth4 + 1 <= stack4;
+        }
+        if (f.fits || f.sah_levels == 0) return f;
+        f.sah_levels = std::max(0, f.sah_levels - kBvhSahStep);
+    }
 }
 
 namespace {

@@ -142,7 +142,7 @@ struct StepObjs {
 void build_step_objs(const DObjBox* boxes, const DObjPlane* planes, int n, StepObjs& SO);
 constexpr uint32_t kBvhLeaf = 4;      // sphere BVH (C3): primitives per leaf (at most)
 constexpr uint32_t kBvhLeafTri = XRT_BVH_LEAF;   // triangle BVH (C4): triangles per leaf (at most)
-constexpr int kBvhMaxDepth = 48;      // BVH build: depth bound (SAH above max - 24 levels, median below)
+constexpr int kBvhMaxDepth = 48;      // BVH build: SAH above level max - kBvhMedianLevels, median below (bvh.h)
 constexpr int kBvhStack = 24;         // k_trace_bvh: LDS traversal stack entries per thread (> tree depth)
 constexpr int kBvh4Stack = 48;        // k_trace_deep4: LDS stack entries per lane (>= 3 * 4-wide depth + 1)
 constexpr int kSphBvhMin = 16;        // sphere scenes with at least this many spheres get a skip-link BVH

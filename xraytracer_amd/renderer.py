@@ -124,6 +124,17 @@ class HipRenderer:
                 self._check(self._lib.xrt_set_medium(self.ctx, C.byref(md)), "xrt_set_medium")
         self._uploaded = scene
 
+    BVH_INFO = ("bvh_nodes", "bvh_stack", "bvh4_nodes", "bvh4_stack", "two_level", "n_snode", "bvh_tris", "stack_entry")
+
+    def bvh_info(self, scene: SceneBundle) -> dict:
+        """What the upload of the scene built for the kernels that walk a hierarchy (xrt_test_bvh_info,
+        a self-test that launches nothing): the BVH_INFO values by name."""
+        if self._uploaded is not scene:
+            self.upload(scene)
+        out = (C.c_int32 * 8)()
+        self._check(self._lib.xrt_test_bvh_info(self.ctx, out), "xrt_test_bvh_info")
+        return dict(zip(self.BVH_INFO, (int(v) for v in out)))
+
     def params(self, scene, width, height, shard_index=0, shard_count=1, timing=False, integrator=None,
                max_depth=None, schedule="auto", slots_per_wave=0, visits_per_launch=0, group=True,
                accumulate=False, deep="auto", spec=True, whitted_bvh=False, overlap=True, interleave=None,
